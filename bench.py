@@ -13,10 +13,13 @@ gradient buffer, an update graph); every kernel on the path is in libsnnflow.so.
     python bench.py [--gpus N --steps K --warmup W --channels C --res R --batch B]
     torchrun --nproc-per-node N bench.py --gpus N ...        (one rank per GPU, RCCL)
 
-Rank 0 prints one JSON line.  `roofline` is for the dominant kernel, timed live with
-HIP events around each of its launches in one extra eager step after the timed
-region; `cpu_baseline` times the CPU oracle (oracle/, a restatement of the
-reference's PyTorch path) on a bounded sample of the same workload.
+Rank 0 prints one JSON line.  A plain run sets up, warms up, times the K steps and prints the
+line; `--dump-outputs DIR` also writes what the last timed step computed as DIR/<name>.npy.
+`--full` adds the measurements that take runs of their own (null in a plain line): `roofline`
+and `kernels` are for the dominant kernel, timed live with HIP events around each of its
+launches in one extra eager step after the timed region; `cpu_baseline` times the CPU oracle
+(oracle/, a restatement of the reference's PyTorch path) on a bounded sample of the same
+workload; with `--eval` also `configs0`.
 """
 import argparse
 import json
@@ -50,7 +53,15 @@ def parse():
     p.add_argument("--no-graph", action="store_true")
     p.add_argument("--per-step", action="store_true",
                    help="T model() calls (FireNetStep) instead of model.forward_sequence (wavefront launches)")
-    p.add_argument("--no-cpu-baseline", action="store_true")
+    p.add_argument("--full", action="store_true",
+                   help="after the timed steps also measure what takes runs of its own: the per-kernel HIP-event "
+                        "timing step (roofline, kernels), the CPU oracle baseline (cpu_baseline) and, with --eval, "
+                        "configs[0] of BASELINE.json (configs0)")
+    p.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU oracle baseline")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps write what the last timed step computed (loss, flows, final states, "
+                        "updated parameters; --eval: flows, AEE / outlier %%, final states) as DIR/<name>.npy, fp32, "
+                        "at most 64 MB in all (a fixed seeded sample of a larger array)")
     p.add_argument("--pool", type=int, default=3, help="distinct synthetic batches cycled in HBM")
     p.add_argument("--dist-backend", default=None,
                    help="nccl (= RCCL; the default when a GPU is present) or gloo (rehearsals, CPU, "
@@ -241,6 +252,7 @@ def main():
     pool = [_pack([make_window(B, N, R, R, gen, dev) for _ in range(T)]) for _ in range(args.pool)]
     static_flat, static_views = _pack_like(pool[0])
     cur = {"views": static_views}  # the windows fwd_bwd reads (graph capture: one resident batch each)
+    kept = {} if args.dump_outputs else None  # --dump-outputs: slot (graph index; eager: 0) -> (loss, flows per window)
 
     def load_batch(i):  # eager steps: one device copy of the next resident batch into the input buffer
         static_flat.copy_(pool[i % len(pool)][0], non_blocking=True)
@@ -273,6 +285,8 @@ def main():
             loss_fn.event_flow_association(outs[t]["flow"], w["event_list"], w["event_list_pol_mask"], w["event_mask"])
         loss = loss_fn()
         loss.backward(seed)  # == loss.backward(): the unit seed is a persistent tensor, not a fill per step
+        if kept is not None:
+            kept[cur.get("slot", 0)] = (loss.detach(), [_flow_list(o["flow"]) for o in outs])
         return loss
 
     sync_grads = dp.GradAllReduce(params)  # one SUM all-reduce over the engine's flat gradient buffer
@@ -323,7 +337,7 @@ def main():
             n_graphs = pingpong.cycle(len(pool))
         for j in range(n_graphs):
             opt.zero_grad(set_to_none=True)
-            cur["views"] = pool[j % len(pool)][1]
+            cur["views"], cur["slot"] = pool[j % len(pool)][1], j
             if pingpong is not None:
                 pingpong.arm(model, j)
             g = torch.cuda.CUDAGraph()
@@ -389,26 +403,39 @@ def main():
     events_per_step = world * B * T * N
     value = events_per_step * args.steps / elapsed
 
-    # live per-kernel timing: one extra eager step with HIP events around every launch
-    # (the stream is first held by a ~40 ms device-side sleep so the host enqueues the
-    # whole step ahead of the GPU: the events then bracket kernel execution only)
-    timer = _lib.KernelTimer()
-    _lib.TIMER = timer
-    load_batch(0)
-    if pingpong is not None:  # the states the graphs hand over (detached views), not a capture's outputs
-        set_states(list(pingpong.views[0]))
-    torch.cuda._sleep(100_000_000)
-    step_eager()
-    _lib.TIMER = None
-    kern = timer.summary()
-    if unet:
-        roofline, kernels = _unet_roofline(kern)
-    else:
-        roofline, kernels = _firenet_roofline(kern, model, args, B, R, T)
+    if kept is not None and rank == 0:  # what the last timed step computed (rank 0's share when N > 1)
+        last = (args.steps - 1) % len(graphs) if graphs else 0
+        loss, flows = kept[last]
+        arrays = {"loss": loss, "params": torch.cat([p.detach().reshape(-1) for p in params])}
+        for i in range(len(flows[0])):  # per flow map: [T, B, 2, H, W]
+            arrays[f"flow_{i}"] = torch.stack([f[i] for f in flows])
+        # the states handed to the next step: the ping-pong buffer the last replay wrote, else the model's
+        final = _flat_tensors(pingpong.views[(last + 1) % 2] if (graphs and pingpong is not None) else get_states())
+        if final is not None:
+            arrays["states"] = final
+        dump_outputs(args.dump_outputs, arrays)
 
-    cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
-        cpu = cpu_baseline_unet(args, pool[0][1]) if unet else cpu_baseline(args, pool[0][1])
+    roofline = kernels = cpu = None
+    if args.full:
+        # live per-kernel timing: one extra eager step with HIP events around every launch
+        # (the stream is first held by a ~40 ms device-side sleep so the host enqueues the
+        # whole step ahead of the GPU: the events then bracket kernel execution only)
+        timer = _lib.KernelTimer()
+        _lib.TIMER = timer
+        load_batch(0)
+        if pingpong is not None:  # the states the graphs hand over (detached views), not a capture's outputs
+            set_states(list(pingpong.views[0]))
+        torch.cuda._sleep(100_000_000)
+        step_eager()
+        _lib.TIMER = None
+        kern = timer.summary()
+        if unet:
+            roofline, kernels = _unet_roofline(kern)
+        else:
+            roofline, kernels = _firenet_roofline(kern, model, args, B, R, T)
+
+        if rank == 0 and world == 1 and not args.no_cpu_baseline:
+            cpu = cpu_baseline_unet(args, pool[0][1]) if unet else cpu_baseline(args, pool[0][1])
 
     if rank == 0:
         line = {
@@ -428,6 +455,45 @@ def main():
         print(json.dumps(line), flush=True)
     if dist_on:
         dist.destroy_process_group()
+
+
+DUMP_BUDGET_BYTES = 60 * 10 ** 6  # --dump-outputs: all files together stay under 64 MB
+
+
+def _flow_list(flow):
+    """A model output's flow maps (a list of [B, 2, H, W] tensors, or one tensor) as detached tensors."""
+    return [f.detach() for f in (flow if isinstance(flow, (list, tuple)) else [flow])]
+
+
+def _flat_tensors(x):
+    """Every tensor of a nested list / tuple (None entries skipped), flattened into one fp32 row."""
+    out = []
+
+    def walk(v):
+        if torch.is_tensor(v):
+            out.append(v.detach().reshape(-1).float())
+        elif isinstance(v, (list, tuple)):
+            for e in v:
+                walk(e)
+
+    walk(x)
+    return torch.cat(out) if out else None
+
+
+def dump_outputs(path, arrays):
+    """Write {name: tensor} as path/<name>.npy in fp32, at most DUMP_BUDGET_BYTES in all: an array
+    over its equal share of the budget is cut to a fixed sample of its flattened elements (sorted
+    indices drawn once from a generator seeded by the array's size: the same elements in every run)."""
+    import numpy as np
+
+    os.makedirs(path, exist_ok=True)
+    share = DUMP_BUDGET_BYTES // (4 * len(arrays))  # elements per array
+    for name, t in arrays.items():
+        t = t.detach().float()
+        if t.numel() > share:
+            idx = np.sort(np.random.default_rng(t.numel()).choice(t.numel(), share, replace=False))
+            t = t.reshape(-1)[torch.from_numpy(idx).to(t.device)]
+        np.save(os.path.join(path, name + ".npy"), t.cpu().numpy())
 
 
 def _dp_check(world, rank, step_parts, params):
@@ -530,6 +596,9 @@ def eval_main(args, world, rank, dev, backend, dist_on=False):
     metric = snnflow.AEE({"loader": {"resolution": [R, R]}, "loss": {"overwrite_intermediate": False}}, dev,
                          flow_scaling=128)
     last = {}  # the last pass's per-window AEE / outlier % (device tensors; read after timing)
+    # --dump-outputs: slot (graph index; eager: 0) -> (flows per window, AEE / outlier % per window)
+    kept = {} if args.dump_outputs else None
+    n_slots = 1 if args.no_graph else StatePingPong.cycle(args.pool)
 
     pingpong = []  # set after the warm-up: graph replays hand the states over copy-free
 
@@ -550,6 +619,8 @@ def eval_main(args, world, rank, dev, backend, dist_on=False):
                                                             "dt_input": one, "dt_gt": one})
             last[t] = metric()
             metric.reset()
+        if kept is not None:
+            kept[j % n_slots] = ([_flow_list(o["flow"]) for o in outs], dict(last))
         if not pingpong:
             handover()
 
@@ -563,17 +634,28 @@ def eval_main(args, world, rank, dev, backend, dist_on=False):
     events_per_step = world * B * T * N
     value = events_per_step * args.steps / elapsed
 
-    timer = _lib.KernelTimer()
-    _lib.TIMER = timer
-    torch.cuda._sleep(100_000_000)
-    with torch.no_grad():
-        eval_pass(0)
-    _lib.TIMER = None
-    roofline, kernels = _firenet_roofline(timer.summary(), model, args, B, R, T)
+    if kept is not None and rank == 0:  # what the last timed pass computed (rank 0's share when N > 1)
+        slot = (args.steps - 1) % n_slots
+        flows, metrics = kept[slot]
+        arrays = {f"flow_{i}": torch.stack([f[i] for f in flows]) for i in range(len(flows[0]))}  # [T, B, 2, H, W]
+        arrays["aee"] = torch.stack([metrics[t][0].reshape(-1) for t in range(T)])  # [T, B]
+        arrays["outliers_percent"] = torch.stack([metrics[t][1].reshape(-1) for t in range(T)])
+        arrays["states"] = _flat_tensors(pingpong[0].views[(slot + 1) % 2] if graphs else model._states)
+        dump_outputs(args.dump_outputs, arrays)
+
+    roofline = kernels = None
+    if args.full:
+        timer = _lib.KernelTimer()
+        _lib.TIMER = timer
+        torch.cuda._sleep(100_000_000)
+        with torch.no_grad():
+            eval_pass(0)
+        _lib.TIMER = None
+        roofline, kernels = _firenet_roofline(timer.summary(), model, args, B, R, T)
 
     # configs[0]: T = 5 windows of one sequence, forward only, GPU and CPU oracle
     cfg1 = None
-    if rank == 0 and world == 1:
+    if args.full and rank == 0 and world == 1:
         m1 = new_model()
         g1 = torch.Generator(device=dev).manual_seed(11)
         wins1 = [make_window(1, N, R, R, g1, dev) for _ in range(5)]
@@ -600,7 +682,7 @@ def eval_main(args, world, rank, dev, backend, dist_on=False):
             cfg1["cpu"] = cpu_baseline_forward(args, wins1)
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         cpu = cpu_baseline_eval(args, pool[0][1], gts[0])
 
     if rank == 0:

@@ -7,7 +7,7 @@ O=gpurun_out/envab
 mkdir -p $O
 for i in $(seq $N); do
   for E in "$A" "$B"; do
-    env $E timeout -k 10 300 python bench.py --no-cpu-baseline $ARGS > $O/run.json 2> $O/run.err || { tail -20 $O/run.err; exit 4; }
+    env $E timeout -k 10 300 python bench.py --full --no-cpu-baseline $ARGS > $O/run.json 2> $O/run.err || { tail -20 $O/run.err; exit 4; }
     python -c "import json;d=json.load(open('$O/run.json'));print('$E', d['ms_per_step'], {k:v['avg_us'] for k,v in list(d['kernels'].items())[:6]})"
   done
 done

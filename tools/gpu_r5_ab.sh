@@ -9,7 +9,7 @@ for rep in 1 2; do
   for spec in base:default ${LIBS:-}; do
     n=${spec%%:*}; path=${spec#*:}
     if [ "$path" = default ]; then unset SNNFLOW_LIB; else export SNNFLOW_LIB=$R/$path; fi
-    timeout -k 10 300 python bench.py --no-cpu-baseline ${BENCH_ARGS:-} > $O/bench_${n}_$rep.json 2> $O/bench_${n}_$rep.err || { echo "bench $n failed"; tail -20 $O/bench_${n}_$rep.err; exit 4; }
+    timeout -k 10 300 python bench.py --full --no-cpu-baseline ${BENCH_ARGS:-} > $O/bench_${n}_$rep.json 2> $O/bench_${n}_$rep.err || { echo "bench $n failed"; tail -20 $O/bench_${n}_$rep.err; exit 4; }
     python -c "import json;d=json.load(open('$O/bench_${n}_$rep.json'));print('$n', d['ms_per_step'], d['value'], d['roofline']['avg_us'], {k:v['avg_us'] for k,v in list(d['kernels'].items())[:9]})"
   done
 done

@@ -8,7 +8,7 @@ mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
 run() {  # name, bench args...
   local n=$1; shift
-  timeout -k 10 400 python3 $R/bench.py --no-cpu-baseline "$@" > $O/line_$n.json 2> $O/line_$n.err || { echo "$n failed"; tail -10 $O/line_$n.err; return 4; }
+  timeout -k 10 400 python3 $R/bench.py --full --no-cpu-baseline "$@" > $O/line_$n.json 2> $O/line_$n.err || { echo "$n failed"; tail -10 $O/line_$n.err; return 4; }
   python3 -c "import json;d=json.load(open('$O/line_$n.json'));print('$n', d['ms_per_step'], d['value'], (d.get('roofline') or {}).get('frac'))"
   timeout -k 10 400 rocprofv3 --kernel-trace --stats -d $O/prof_$n -o run --output-format csv -- python3 $R/bench.py --no-cpu-baseline --steps 3 --warmup 2 "$@" > $O/prof_$n.json 2> $O/prof_$n.err || { echo "$n rocprof failed"; tail -10 $O/prof_$n.err; return 5; }
   python3 $R/tools/kstats.py $O/prof_$n/run_kernel_stats.csv 12

@@ -10,7 +10,7 @@ grep -E "passed|failed|^FAILED|grad rel-L2 worst|bit planes" $O/tests.log | tail
 [ $rc -ne 0 ] && { grep -E "^E " $O/tests.log | head -20; exit $rc; }
 for i in 1 2; do
   for E in ${AB:-X=0}; do
-    env $E timeout -k 10 300 python bench.py --no-cpu-baseline --channels 32 > $O/c32.json 2> $O/c32.err || { tail -20 $O/c32.err; exit 5; }
+    env $E timeout -k 10 300 python bench.py --full --no-cpu-baseline --channels 32 > $O/c32.json 2> $O/c32.err || { tail -20 $O/c32.err; exit 5; }
     python -c "import json;d=json.load(open('$O/c32.json'));print('$E c32', d['ms_per_step'], {k:v['avg_us'] for k,v in list(d['kernels'].items())[:9]})"
   done
 done

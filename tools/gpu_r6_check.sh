@@ -9,5 +9,5 @@ tail -2 $O/gpu_tests.log
 [ $rc -ne 0 ] && { grep -E "^FAILED|^E " $O/gpu_tests.log | head -20; exit $rc; }
 timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1 || { tail -20 $O/smoke.log; exit 3; }
 tail -1 $O/smoke.log
-timeout -k 10 400 python bench.py > $O/bench.json 2> $O/bench.err || { tail -30 $O/bench.err; exit 4; }
+timeout -k 10 400 python bench.py --full > $O/bench.json 2> $O/bench.err || { tail -30 $O/bench.err; exit 4; }
 python -c "import json;d=json.load(open('$O/bench.json'));print('bench', d['ms_per_step'], d['value'], d['roofline']['frac'], (d.get('cpu_baseline') or {}).get('value'))"

@@ -3,7 +3,7 @@ set -u
 O=gpurun_out/r6c4
 mkdir -p $O
 for i in 1 2; do
-SNNFLOW_BENCH_PROFILE=1 timeout -k 10 300 python bench.py --no-cpu-baseline --per-step --no-graph --steps 40 --warmup 5 > $O/eager$i.json 2> $O/eager_prof$i.txt || { tail -20 $O/eager_prof$i.txt; exit 4; }
+SNNFLOW_BENCH_PROFILE=1 timeout -k 10 300 python bench.py --full --no-cpu-baseline --per-step --no-graph --steps 40 --warmup 5 > $O/eager$i.json 2> $O/eager_prof$i.txt || { tail -20 $O/eager_prof$i.txt; exit 4; }
 python -c "import json;d=json.load(open('$O/eager$i.json'));print('eager', d['ms_per_step'])"
 done
 head -60 $O/eager_prof2.txt | cut -c1-200

@@ -10,7 +10,7 @@ grep -E "passed|failed" $O/gpu_tests.log | tail -2
 if [ $rc -ne 0 ]; then grep -E "^FAILED|^E " $O/gpu_tests.log | head -30; exit $rc; fi
 timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1 || { echo "smoke failed"; tail -20 $O/smoke.log; exit 3; }
 tail -1 $O/smoke.log
-timeout -k 10 400 python bench.py ${BENCH_ARGS:-} > $O/bench.json 2> $O/bench.err || { echo "bench failed"; tail -30 $O/bench.err; exit 4; }
+timeout -k 10 400 python bench.py --full ${BENCH_ARGS:-} > $O/bench.json 2> $O/bench.err || { echo "bench failed"; tail -30 $O/bench.err; exit 4; }
 python -c "import json;d=json.load(open('$O/bench.json'));print('bench', d['ms_per_step'], d['value'], d['roofline']['frac'], d['roofline']['avg_us'], (d.get('cpu_baseline') or {}).get('value')); print({k:v['avg_us'] for k,v in d['kernels'].items()})"
 for l in ${LINES:-c32 unet}; do
   case $l in
@@ -21,6 +21,6 @@ for l in ${LINES:-c32 unet}; do
     eager) a="--per-step --no-graph" ;;
     eval) a="--eval" ;;
   esac
-  timeout -k 10 400 python bench.py --no-cpu-baseline $a > $O/line_$l.json 2> $O/line_$l.err || { echo "$l failed"; tail -10 $O/line_$l.err; exit 5; }
+  timeout -k 10 400 python bench.py --full --no-cpu-baseline $a > $O/line_$l.json 2> $O/line_$l.err || { echo "$l failed"; tail -10 $O/line_$l.err; exit 5; }
   python -c "import json;d=json.load(open('$O/line_$l.json'));print('$l', d['ms_per_step'], d['value'], (d.get('roofline') or {}).get('frac'), {k:v['avg_us'] for k,v in list(d.get('kernels',{}).items())[:10]})"
 done

@@ -9,6 +9,6 @@ rc=$?
 grep -E "passed|failed|^FAILED" $O/tests.log | tail -4
 [ $rc -ne 0 ] && { grep -E "^E " $O/tests.log | head -20; exit $rc; }
 for a in "" "" "--channels 32" "--per-step" "--per-step --no-graph"; do
-  timeout -k 10 300 python bench.py --no-cpu-baseline $a > $O/b.json 2> $O/b.err || { tail -20 $O/b.err; exit 5; }
+  timeout -k 10 300 python bench.py --full --no-cpu-baseline $a > $O/b.json 2> $O/b.err || { tail -20 $O/b.err; exit 5; }
   python -c "import json;d=json.load(open('$O/b.json'));print('$a', d['ms_per_step'], {k:v['avg_us'] for k,v in list(d.get('kernels',{}).items())[:8]})"
 done

@@ -7,7 +7,7 @@ mkdir -p $O
 i=0
 for E in ${AB:-X=0}; do
   i=$((i+1))
-  env SNNFLOW_UNET_SHAPES=1 $E timeout -k 10 400 python bench.py --no-cpu-baseline --model SpikingRecEVFlowNet --steps 3 --warmup 2 > $O/u$i.json 2> $O/u$i.err || { tail -20 $O/u$i.err; exit 5; }
+  env SNNFLOW_UNET_SHAPES=1 $E timeout -k 10 400 python bench.py --full --no-cpu-baseline --model SpikingRecEVFlowNet --steps 3 --warmup 2 > $O/u$i.json 2> $O/u$i.err || { tail -20 $O/u$i.err; exit 5; }
   python - $O/u$i.json "$E" "${PAT:-conv|dgrad|wgrad}" <<'PY'
 import json, re, sys
 d = json.load(open(sys.argv[1])); pat = re.compile(sys.argv[3])

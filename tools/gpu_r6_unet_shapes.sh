@@ -3,7 +3,7 @@
 set -u
 O=gpurun_out/r6shapes${TAG:-}
 mkdir -p $O
-SNNFLOW_UNET_SHAPES=1 timeout -k 10 400 python bench.py --no-cpu-baseline --model SpikingRecEVFlowNet --steps 3 --warmup 2 > $O/unet.json 2> $O/unet.err || { tail -20 $O/unet.err; exit 5; }
+SNNFLOW_UNET_SHAPES=1 timeout -k 10 400 python bench.py --full --no-cpu-baseline --model SpikingRecEVFlowNet --steps 3 --warmup 2 > $O/unet.json 2> $O/unet.err || { tail -20 $O/unet.err; exit 5; }
 python - <<PY
 import json
 d=json.load(open('$O/unet.json'))
