@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define SNNFLOW_ABI_VERSION 40
+#define SNNFLOW_ABI_VERSION 41
 
 #define SNNFLOW_E_ARG (-1)      /* invalid argument / unsupported shape */
 #define SNNFLOW_E_CHANNELS (-2) /* channel count without a compiled kernel */
@@ -378,6 +378,67 @@ typedef struct snnflow_encode_args {
     float* cnt; float* voxel; float* image; float* mask; float* pol_mask;
 } snnflow_encode_args;
 int snnflow_encode_events(const snnflow_encode_args* a, void* stream);
+
+/* ---- on-device batch preparation (ABI 41) ----
+ * Everything the reference's loader does between "raw events of a window, as read from the
+ * file" and the dict the loop consumes (dataloader/h5.py:285-333 formatting, augmentation,
+ * encodings, hot-pixel removal; h5.py:373-437 average-pool downsampling and the rescaled event
+ * list; dataloader/base.py:71-99 event_formatting, 101-127 augment_events, 144-159
+ * augment_flowmap, 237-256 create_hot_mask; dataloader/encodings.py:88-103 get_hot_event_mask),
+ * batched over the B slots of a batch.
+ *
+ * Slot b holds N raw events xs/ys/ts/ps [B][N] (ps in {0, 1}, ts already fp32) of which the
+ * first counts[b] are valid (all N when counts is NULL).  Per slot, over its valid events:
+ *   p = 2*ps - 1;  ts = (ts - min) / (max - min) (fp32; all zeros unless max - min > 0);
+ *   flags[b] bit SNNFLOW_AUG_H: x = W0-1-x, bit _V: y = H0-1-y, bit _P: p = -p.
+ * The encodings are built at the full resolution H0 x W0 exactly as snnflow_encode_events
+ * defines them.  With hot_enabled, per slot: hot_events += (cnt_pos + cnt_neg > 0),
+ * hot_idx += 1, rate = hot_events / hot_idx; when hot_idx > hot_min_obvs the (at most)
+ * hot_max_px pixels of highest rate among those with rate > hot_max_rate -- ties to the
+ * lowest flat index, which is what hot_max_px rounds of argmax select -- are zeroed in
+ * event_cnt, event_voxel and event_mask (not in the event list, as in the reference).
+ * Pooling applies when Ht < H0 or Wt < W0 (H0 % Ht == 0 and W0 % Wt == 0 required; without
+ * pooling Ht == H0 and Wt == W0): every output pixel is the row-major fp32 sum of its
+ * (H0/Ht) x (W0/Wt) window divided by the window size (F.avg_pool2d), the list's y / x are
+ * multiplied by scale_y / scale_x (the caller's fp32(Ht/H0), fp32(Wt/W0)) and clamped to
+ * [0, Ht-1] / [0, Wt-1].  gtflow_in (optional) is flipped like the events (component 0 negated
+ * by a horizontal, component 1 by a vertical flip) and pooled unless keep_gt_full_res, which
+ * also keeps event_mask at full resolution.  Rows of padding events (index >= counts[b]) in
+ * event_list / pol_mask are zeros.  Counts, masks, lists and gtflow are exact; voxel sums
+ * follow the atomic arrival order.  All outputs are fully written; no host synchronisation. */
+#define SNNFLOW_AUG_H 1
+#define SNNFLOW_AUG_V 2
+#define SNNFLOW_AUG_P 4
+typedef struct snnflow_loader_args {
+    int B, N;
+    int H0, W0;                 /* full resolution (BaseDataLoader.resolution, base.py:24-27) */
+    int Ht, Wt;                 /* target resolution (loader.resolution) */
+    int num_bins, round_ts;
+    int keep_gt_full_res;       /* pooled only: event_mask and gtflow stay [.][H0][W0] */
+    int hot_enabled, hot_max_px, hot_min_obvs;
+    float hot_max_rate;         /* already rounded to fp32 */
+    float scale_y, scale_x;     /* pooled only: fp32(Ht/H0), fp32(Wt/W0) */
+    const float* xs; const float* ys; const float* ts; const float* ps;   /* [B][N] raw events */
+    const int* counts;          /* [B] valid events per slot, or NULL = N */
+    const int* flags;           /* [B] SNNFLOW_AUG_* bits, or NULL = none */
+    const float* gtflow_in;     /* [B][2][H0][W0] or NULL */
+    float* hot_events;          /* [B][H0][W0] state, updated (hot_enabled) */
+    int* hot_idx;               /* [B] state, updated (hot_enabled) */
+    float* event_cnt;           /* [B][2][Ht][Wt] */
+    float* event_voxel;         /* [B][num_bins][Ht][Wt] */
+    float* event_mask;          /* [B][1][Ht][Wt], or [B][1][H0][W0] when pooled with keep_gt_full_res */
+    float* event_list;          /* [B][N][4] (ts, y, x, p) */
+    float* pol_mask;            /* [B][N][2] */
+    float* gtflow;              /* [B][2][Ht][Wt] ([H0][W0] with keep_gt_full_res); NULL iff gtflow_in is */
+    float* scratch;             /* snnflow_loader_scratch_floats(...) floats, contents don't care */
+} snnflow_loader_args;
+/* 2 launches (min/max + zeroing, event pass), +2 with hot_enabled (state update + candidate
+ * list, selection), +1 with hot_enabled, pooling or gtflow (mask-multiply / pool / flow flip). */
+int snnflow_loader_prepare(const snnflow_loader_args* a, void* stream);
+/* Floats of scratch the call above needs for these sizes (min/max partials; with pooling the
+ * full-resolution cnt / voxel / mask; with the hot filter its mask and candidate lists). */
+int64_t snnflow_loader_scratch_floats(int B, int N, int H0, int W0, int Ht, int Wt, int num_bins, int hot_enabled,
+                                      int keep_gt_full_res);
 
 /* Sums per-block weight-gradient slabs: out[i][e] = sum_b slab[i][b][e]. */
 typedef struct snnflow_slab_desc { const float* slab; float* out; int elems; } snnflow_slab_desc;

@@ -10,6 +10,8 @@ from .cells import ConvLayer, Leaky, SNNtorch_ConvLIF, SNNtorch_ConvLIFRecurrent
 from .norm import MPBN, TEBN
 from .convlif import ConvLIF, ConvLIFRecurrent
 from . import checkpoint, encodings  # noqa: F401  (checkpoint interchange, on-device event encodings)
+from . import loader  # noqa: F401  (on-device batch preparation)
+from .loader import BatchPreparer
 from .loss import EventWarping
 from .metrics import AAE, AAE_Filtered, AAE_Weighted, AE_ofMeans, AEE, NAAE, NEE
 from .optim import ClipAdam
@@ -21,4 +23,4 @@ __all__ = ["LIFFireNet", "LIFFireNet_short", "LIFFireFlowNet", "LIFFireFlowNet_s
            "SNNtorch_ConvLIFRecurrent", "ConvLIF", "ConvLIFRecurrent", "ConvLayer", "Leaky", "EventWarping", "AEE",
            "NEE", "AAE", "NAAE", "AE_ofMeans", "AAE_Weighted", "AAE_Filtered", "SpikingRecEVFlowNet",
            "SpikingMultiResUNetRecurrent", "SpikingRecurrentConvLayer", "SpikingResidualBlock", "SpikingUpsampleConvLayer",
-           "ClipAdam", "SnnflowError", "check_device_errors"]
+           "ClipAdam", "SnnflowError", "check_device_errors", "BatchPreparer"]

@@ -18,7 +18,7 @@ F32 = ctypes.c_float
 F64 = ctypes.c_double
 
 TILE_H, TILE_W = 8, 32
-ABI_VERSION = 40
+ABI_VERSION = 41
 THETA_SCRATCH = 1024 * 32  # SNNFLOW_THETA_SCRATCH
 
 
@@ -123,6 +123,20 @@ class EncodeArgs(ctypes.Structure):
     _fields_ = [("B", I32), ("N", I32), ("H", I32), ("W", I32), ("ts", P), ("ys", P), ("xs", P), ("ps", P),
                 ("ev_stride", I64), ("batch_stride", I64), ("num_bins", I32), ("round_ts", I32),
                 ("accumulate", I32), ("cnt", P), ("voxel", P), ("image", P), ("mask", P), ("pol_mask", P)]
+
+
+AUG_H, AUG_V, AUG_P = 1, 2, 4  # SNNFLOW_AUG_*
+
+
+class LoaderArgs(ctypes.Structure):
+    _fields_ = [("B", I32), ("N", I32), ("H0", I32), ("W0", I32), ("Ht", I32), ("Wt", I32),
+                ("num_bins", I32), ("round_ts", I32), ("keep_gt_full_res", I32),
+                ("hot_enabled", I32), ("hot_max_px", I32), ("hot_min_obvs", I32), ("hot_max_rate", F32),
+                ("scale_y", F32), ("scale_x", F32),
+                ("xs", P), ("ys", P), ("ts", P), ("ps", P), ("counts", P), ("flags", P), ("gtflow_in", P),
+                ("hot_events", P), ("hot_idx", P),
+                ("event_cnt", P), ("event_voxel", P), ("event_mask", P), ("event_list", P), ("pol_mask", P),
+                ("gtflow", P), ("scratch", P)]
 
 
 class AeeArgs(ctypes.Structure):
@@ -301,7 +315,9 @@ EXPORTS = {
     "snnflow_wgrad": (I32, [ctypes.POINTER(WgradArgs), P]),
     "snnflow_convlif_fwd": (I32, [ctypes.POINTER(ConvLifFwdArgs), P]),
     "snnflow_encode_events": (I32, [ctypes.POINTER(EncodeArgs), P]),
-    "snnflow_pol_iwe": (I32, [P, P, P, I64, I32, I32, I32, I32, I32, F32, F32, I32, P, P]),
+    "snnflow_loader_prepare": (I32, [ctypes.POINTER(LoaderArgs), P]),
+    "snnflow_loader_scratch_floats": (I64, [I32, I32, I32, I32, I32, I32, I32, I32, I32]),
+    "snnflow_pol_iwe":(I32, [P, P, P, I64, I32, I32, I32, I32, I32, F32, F32, I32, P, P]),
     "snnflow_aee": (I32, [ctypes.POINTER(AeeArgs), P]),
     "snnflow_aee_acc_doubles": (I32, [I32, I32, I32]),
     "snnflow_flow_metrics": (I32, [ctypes.POINTER(FlowMetricsArgs), P]),
