@@ -577,6 +577,97 @@ typedef struct snnflow_flow_metrics_args {
 int snnflow_flow_metrics(const snnflow_flow_metrics_args* a, void* stream);
 int snnflow_flow_metrics_rows(int B, int H, int W);
 
+/* ---- visual evaluation (eval_flow.py:262-340 with vis.store / metrics.heat_map) ----
+ * The device renders the frames the reference's Visualization draws on the host
+ * (utils/visualization.py) and the per-pixel error maps its metrics keep for heatmaps
+ * (loss/flow.py:443-525), so only finished frames cross to the host.  Additive entries:
+ * the ABI version is unchanged.  Inputs must be finite: NaN / Inf are unsupported (the
+ * radix order of the select below is the order of finite floats; -0 counts as +0).
+ *
+ * Percentiles: np.percentile(x, q) (method "linear") of every plane x[p][0..n), exact.  One
+ * block per plane finds the order statistics floor(vi) and floor(vi)+1 around every
+ * requested rank vi = (n-1)*q/100 by a 4-pass radix select (8 bits a pass, one LDS
+ * histogram per distinct key prefix, every quantile resolved in the same passes; no sort,
+ * no global atomics, no scratch), then interpolates as numpy's _lerp does:
+ *   r = a + (b-a)*g, replaced by b - (b-a)*(1-g) when g >= 0.5       (g = vi - floor(vi)).
+ * fp64 = 1: x widened to double, q/100, vi, g and the lerp in fp64 (np.percentile of
+ * x.astype(float64)), out [nplanes][nq] doubles.  fp64 = 0: q32 = (float)q / 100.f,
+ * vi = (float)(n-1) * q32, g and the lerp in fp32 (np.percentile of a float32 array),
+ * out [nplanes][nq] floats.  1 <= nq <= SNNFLOW_VIS_MAX_Q, 0 <= q <= 100, 1 <= n <= 2^24. */
+#define SNNFLOW_VIS_MAX_Q 4
+typedef struct snnflow_percentiles_args {
+    int nplanes, n, nq, fp64;
+    const float* x;             /* [nplanes][n] */
+    double q[SNNFLOW_VIS_MAX_Q]; /* percentages */
+    void* out;                  /* [nplanes][nq] double (fp64) or float */
+} snnflow_percentiles_args;
+int snnflow_percentiles(const snnflow_percentiles_args* a, void* stream);
+
+/* Visualization.flow_to_image (utils/visualization.py:649-709) per image b of a batch:
+ * mag = (double)sqrtf(x*x + y*y); stats[b] = {min, max, p5, p95} of mag (fp64 percentiles,
+ * the magnitude recomputed in every select pass, never stored); hue = (atan2f(y, x) +
+ * (float)pi) * (float)(1/pi/2) in fp32; value in fp64: with max - min > 0
+ * clip(sqrt(clip((mag-p5)/(p95-p5+1e-8), 0, 1))*1.3 + 0.15, 0.15, 1), else with max > 0
+ * clip(sqrt(mag/max [* uniform_v])*1.3 + 0.15, 0.15, 1), else 0; 0 wherever mag == 0;
+ * saturation 1; matplotlib's hsv_to_rgb in fp64; each channel (uint8)(255*c).
+ * 2 launches (select, render: one thread per pixel). */
+typedef struct snnflow_flow_to_image_args {
+    int B, H, W;
+    const float* flow;          /* [B][2][H][W], channel 0 = x */
+    int has_uniform_v;          /* 0: uniform_v = None */
+    double uniform_v;
+    double* stats;              /* out [B][4]: min, max, p5, p95 of the magnitude */
+    uint8_t* out;               /* out [B][H][W][3] RGB */
+} snnflow_flow_to_image_args;
+int snnflow_flow_to_image(const snnflow_flow_to_image_args* a, void* stream);
+
+/* Visualization.events_to_image (utils/visualization.py:1037-1084) per image: p1 / p99 of
+ * each polarity plane (fp32 percentiles), max = the larger p99, each plane (v - p1) / (max -
+ * p1) unless p1 == max, clipped to [0, 1].  gray = 0 ("green_red"): out [B][H][W][3] =
+ * (neg, pos, 0) (the assignment order of :1070-1082); gray = 1: out [B][H][W] =
+ * (float)(0.5 + (double)(0.5f*pos + -0.5f*neg)).  2 launches. */
+typedef struct snnflow_events_to_image_args {
+    int B, H, W, gray;
+    const float* cnt;           /* [B][2][H][W] */
+    float* stats;               /* out [B][2][2]: (p1, p99) of the positive, then the negative plane */
+    float* out;
+} snnflow_events_to_image_args;
+int snnflow_events_to_image(const snnflow_events_to_image_args* a, void* stream);
+
+/* Visualization.minmax_norm (utils/visualization.py:1025-1034) per plane: den = p99 - p1
+ * (fp32 percentiles); (x - p1) / den when den != 0; clipped to [0, 1].  2 launches. */
+typedef struct snnflow_minmax_norm_args {
+    int B, n;                   /* B planes of n = H*W values */
+    const float* x;             /* [B][n] */
+    float* stats;               /* out [B][2]: p1, p99 */
+    float* out;                 /* out [B][n] */
+} snnflow_minmax_norm_args;
+int snnflow_minmax_norm(const snnflow_minmax_norm_args* a, void* stream);
+
+/* Visualization.error_to_image (utils/visualization.py:618-645) for n pixels: v = clip((err *
+ * (180.f/(float)pi)) / 180.f, 0, 1) in fp32; out[i] = ((uint8)(v*255.f), 0, 0).  (The reference
+ * renders sample 0 of a batch; every sample is rendered here.)  1 launch. */
+int snnflow_error_to_image(const float* err, int64_t n, uint8_t* out, void* stream);
+
+/* Per-pixel error maps and their aggregation for heatmaps (loss/flow.py:618-631 AEE, :729-747
+ * AAE, :790-808 NAAE, :489-511 accumulate_error_heatmap).  With flow', valid and the per-pixel
+ * expressions exactly as in snnflow_flow_metrics: err[b][p] = the metric's UNMASKED error
+ * (SNNFLOW_EM_AEE: |f'-g|; _AAE: acos(clamp(|f'||g| / (f'.g + 0.01))); _NAAE:
+ * acos(clamp(f'.g / (|f'||g| + 1e-9))) / (|f'| + 1e-9)), and the persistent accumulators
+ * sum[p] += sum_b err[b][p]*valid[b][p], count[p] += sum_b valid[b][p] (b in order; one thread
+ * owns a pixel: no atomics, bit-reproducible).  sum / count NULL: error map only.  1 launch. */
+#define SNNFLOW_EM_AEE 0
+#define SNNFLOW_EM_AAE 1
+#define SNNFLOW_EM_NAAE 2
+typedef struct snnflow_error_maps_args {
+    int B, H, W, metric;
+    const float* flow; const float* gtflow; const float* event_mask; const float* dt_ratio;  /* as snnflow_flow_metrics */
+    float flow_scaling;
+    float* err;                 /* out [B][H][W] */
+    float* sum; float* count;   /* in/out [H][W] each, or both NULL */
+} snnflow_error_maps_args;
+int snnflow_error_maps(const snnflow_error_maps_args* a, void* stream);
+
 /* HIP twin of the export op SNN_implementation::LIF (ONNX_LIF_operator/src/lif_op.cpp:8-56):
  * m' = beta[c]*mem + x; spk = m' >= thr[c]; mem_out = spk ? 0 : m'  (NCHW). */
 int snnflow_lif_export(const float* x, const float* mem, const float* beta, const float* thr,

@@ -12,6 +12,7 @@ from .convlif import ConvLIF, ConvLIFRecurrent
 from . import checkpoint, encodings  # noqa: F401  (checkpoint interchange, on-device event encodings)
 from . import loader  # noqa: F401  (on-device batch preparation)
 from .loader import BatchPreparer
+from . import vis  # noqa: F401  (on-device frame renderers and percentiles)
 from .loss import EventWarping
 from .metrics import AAE, AAE_Filtered, AAE_Weighted, AE_ofMeans, AEE, NAAE, NEE
 from .optim import ClipAdam

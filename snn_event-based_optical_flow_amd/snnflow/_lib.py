@@ -150,6 +150,33 @@ class FlowMetricsArgs(ctypes.Structure):
                 ("dt_ratio", P), ("flow_scaling", F32), ("mag_threshold", F32), ("rows", P), ("out", P)]
 
 
+VIS_MAX_Q = 4  # SNNFLOW_VIS_MAX_Q
+EM_AEE, EM_AAE, EM_NAAE = 0, 1, 2  # SNNFLOW_EM_*
+
+
+class PercentilesArgs(ctypes.Structure):
+    _fields_ = [("nplanes", I32), ("n", I32), ("nq", I32), ("fp64", I32), ("x", P), ("q", F64 * VIS_MAX_Q),
+                ("out", P)]
+
+
+class FlowToImageArgs(ctypes.Structure):
+    _fields_ = [("B", I32), ("H", I32), ("W", I32), ("flow", P), ("has_uniform_v", I32), ("uniform_v", F64),
+                ("stats", P), ("out", P)]
+
+
+class EventsToImageArgs(ctypes.Structure):
+    _fields_ = [("B", I32), ("H", I32), ("W", I32), ("gray", I32), ("cnt", P), ("stats", P), ("out", P)]
+
+
+class MinmaxNormArgs(ctypes.Structure):
+    _fields_ = [("B", I32), ("n", I32), ("x", P), ("stats", P), ("out", P)]
+
+
+class ErrorMapsArgs(ctypes.Structure):
+    _fields_ = [("B", I32), ("H", I32), ("W", I32), ("metric", I32), ("flow", P), ("gtflow", P), ("event_mask", P),
+                ("dt_ratio", P), ("flow_scaling", F32), ("err", P), ("sum", P), ("count", P)]
+
+
 ADAM_MAX_TENSORS = 64  # SNNFLOW_ADAM_MAX_TENSORS
 CLIP_ADAM_MAX_N = 1 << 20  # SNNFLOW_CLIP_ADAM_MAX_N
 
@@ -322,6 +349,12 @@ EXPORTS = {
     "snnflow_aee_acc_doubles": (I32, [I32, I32, I32]),
     "snnflow_flow_metrics": (I32, [ctypes.POINTER(FlowMetricsArgs), P]),
     "snnflow_flow_metrics_rows": (I32, [I32, I32, I32]),
+    "snnflow_percentiles": (I32, [ctypes.POINTER(PercentilesArgs), P]),
+    "snnflow_flow_to_image": (I32, [ctypes.POINTER(FlowToImageArgs), P]),
+    "snnflow_events_to_image": (I32, [ctypes.POINTER(EventsToImageArgs), P]),
+    "snnflow_minmax_norm": (I32, [ctypes.POINTER(MinmaxNormArgs), P]),
+    "snnflow_error_to_image": (I32, [P, I64, P, P]),
+    "snnflow_error_maps": (I32, [ctypes.POINTER(ErrorMapsArgs), P]),
     "snnflow_convlif_bwd": (I32, [ctypes.POINTER(ConvLifBwdArgs), P]),
     "snnflow_convlif_param_grads": (I32, [P, P, P, I32, I32, P, P, P]),
     "snnflow_slab_reduce": (I32, [ctypes.POINTER(SlabDesc), I32, I32, P]),
