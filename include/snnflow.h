@@ -266,6 +266,21 @@ int snnflow_fwd_slot(const snnflow_conv_fwd_args* conv, int nconv, const snnflow
 int snnflow_bwd_slot(const snnflow_layer_bwd_args* layer, int nlayer, const snnflow_lif_bwd_args* lif,
                      void* stream);
 int snnflow_slot_supported(int c, int cin0);
+/* Backward launch with chained pairs (additive; the ABI version is unchanged).  Up to
+ * SNNFLOW_MAX_CHAIN_TASKS layer tasks and the optional top task, under snnflow_bwd_slot's rules, plus:
+ * pair (NULL: none; else nlayer flags) marks with pair[i] != 0 that tasks i and i + 1 are a chained pair.
+ * The backward task of a recurrent layer r at step t+1 hands the gradient of the previous step's spikes
+ * to the task of layer r+1 at step t, pixel by pixel and channel quad by channel quad, so one block per
+ * tile runs the first task and then the second and the value never leaves the block: the two-launch
+ * loop around a recurrent layer becomes one launch per step.  A pair is (c = cin = 8 recurrent LIF-fed
+ * task, c = cin = 8 feed-forward LIF-fed task) of equal shape, both with the fused weight gradients
+ * (wslab_*; the first with s_prev), the second's layer l-1 being the first's layer (same neuron
+ * parameters).  The hand-over replaces the first task's g_state_prev store and the second task's
+ * prev_g_state load: both fields must be NULL.  Everything else each task does is what it does alone.
+ * Malformed pairs are refused before anything is launched. */
+#define SNNFLOW_MAX_CHAIN_TASKS 7
+int snnflow_bwd_chain(const snnflow_layer_bwd_args* layer, int nlayer, const unsigned char* pair,
+                      const snnflow_lif_bwd_args* lif, void* stream);
 /* Tuning (ABI 27): tiles per block of the c = 8 LIF-fed forward tasks of the wavefront launches
  * (0: one tile per block; >= 1: the tile pipeline, which overlaps the next tile's halo loads by
  * LDS-DMA with this tile's math).  Process-wide; default from SNNFLOW_PIPE_FWD at load time.  Results

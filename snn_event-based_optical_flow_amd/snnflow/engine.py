@@ -211,6 +211,12 @@ class FireNetEngine:
         # the slots +2-4 us per launch); C = 8 neutral to +5 us, so off there.  SNNFLOW_FUSE_HEAD=0 / 1 forces.
         fh = os.environ.get("SNNFLOW_FUSE_HEAD")
         self.fuse_head = (self.C >= 16) if fh is None else fh != "0"
+        # FireNetSequence backward at C = 8 with the fused weight gradients: the launches of
+        # chained_bwd_slots (the task of a recurrent layer chained to its consumer's in one block,
+        # snnflow_bwd_chain; T + L launches for LIFFireNet instead of 2(T-1) + L + 1).
+        # SNNFLOW_BWD_CHAIN=0 / 1 forces today's wavefront launches / the chained schedule.
+        bc = os.environ.get("SNNFLOW_BWD_CHAIN")
+        self.bwd_chain = True if bc is None else bc != "0"
         # forward_sequence: spike bit planes between its kernels (ABI 39; SNNFLOW_SPK_BITS=0: the fp32 spike
         # half of the states everywhere, as before)
         self.spk_bits = os.environ.get("SNNFLOW_SPK_BITS", "1") != "0"
@@ -1183,6 +1189,79 @@ def wavefront_slots(T, K):
     return slots
 
 
+def chainable_layers(rec):
+    """Recurrent layers r whose backward task (r, t+1) can run chained to task (r+1, t): r is LIF-fed
+    (not the head), layer r+1 is a feed-forward layer below the top (its task consumes the gradient of
+    r's spikes; for the last layer the top task does, and an adjacent recurrent layer r+1 would close a
+    second loop through the same block)."""
+    L = len(rec)
+    return [r for r in range(1, L - 1) if rec[r] and not rec[r + 1]]
+
+
+def chained_bwd_slots(T, rec, chain=(), max_tasks=_lib.MAX_CHAIN_TASKS):
+    """Launches of the backward of a T-step window over layers 0..L-1 (rec[l]: recurrent); task (k, t)
+    is the backward task of layer k at step t, (L, t) the top task.  Task (k, t) follows
+      (k+1, t)    g_cur and the BatchNorm-backward sums of layer k,
+      (k, t+1)    the same layer's later step (parameter gradients and slab rows are read-modify-write
+                  in descending t, so one layer's tasks sit in distinct launches in that order),
+      (k-1, t+1)  where layer k-1 is recurrent: the gradient of its spikes at step t.
+    For r in `chain` the tasks (r, t+1) and (r+1, t) form one node, a chained pair run by one block per
+    tile (snnflow_bwd_chain): the third dependency stays inside the node, so the loop around layer r
+    costs one launch per step, not two.  A node goes into the launch after its latest dependency (its
+    longest-path level: the same-layer order skews the steps into a wavefront, so the launches fill
+    evenly), or the next one with room for its tasks (max_tasks layer tasks per launch).
+    Returns [[node, ...] per launch], node = ((k, t),) or ((r, t+1), (r+1, t)), layers descending."""
+    L = len(rec)
+    chain = set(chain)
+    if not all(1 <= r < L - 1 and rec[r] and not rec[r + 1] for r in chain):
+        raise ValueError("chained_bwd_slots: a chained layer is recurrent, LIF-fed and followed by a feed-forward layer")
+    node_of = {}
+    for k in range(L + 1):
+        for t in range(T):
+            if k in chain and t >= 1:
+                node = ((k, t), (k + 1, t - 1))
+            elif k - 1 in chain and t <= T - 2:
+                node = ((k - 1, t + 1), (k, t))
+            else:
+                node = ((k, t),)
+            node_of[(k, t)] = node
+
+    def deps(node):
+        out = set()
+        for k, t in node:
+            if k < L:
+                out.add((k + 1, t))
+            if t + 1 < T:
+                out.add((k, t + 1))
+                if k >= 1 and rec[k - 1]:
+                    out.add((k - 1, t + 1))
+        return {node_of[d] for d in out if d not in node}
+
+    level = {}
+
+    def lvl(node):  # longest path from a source (depth <= T + L nodes)
+        if node not in level:
+            level[node] = 1 + max((lvl(d) for d in deps(node)), default=-1)
+        return level[node]
+
+    nodes = sorted(set(node_of.values()), key=lambda n: (lvl(n), -n[0][0], -n[0][1]))
+    slot, fill, launches = {}, [], []
+    for n in nodes:
+        s = 1 + max((slot[d] for d in deps(n)), default=-1)
+        nl = sum(1 for k, _ in n if k < L)
+        while s < len(fill) and fill[s] + nl > max_tasks:
+            s += 1
+        while len(launches) <= s:
+            launches.append([])
+            fill.append(0)
+        slot[n] = s
+        fill[s] += nl
+        launches[s].append(n)
+    for la in launches:
+        la.sort(key=lambda n: -n[0][0])
+    return launches
+
+
 def _state_rows(st_all, fin, T):
     """Flat per-step state rows of a FireNetSequence call: st_all's rows, the last one replaced by
     the caller's final_state_out buffer when there is one (st_all then has T - 1 rows)."""
@@ -1197,7 +1276,9 @@ class FireNetSequence(torch.autograd.Function):
     issued as wavefront launches (``wavefront_slots``, ``snnflow_fwd_slot`` /
     ``snnflow_bwd_slot``) that each run up to four independent layer-steps: a single
     layer-step of C = 8 at 128x128 occupies the chip for one latency-bound block round, so
-    the (L+1) x T launches of the per-step path are replaced by 2(T-1)+L+1.  Batch-sum
+    the (L+1) x T launches of the per-step path are replaced by 2(T-1)+L+1.  The backward at C = 8
+    runs the chained schedule instead (``chained_bwd_slots``, ``snnflow_bwd_chain``): the task of a
+    recurrent layer and its consumer's in one block, T + L launches for LIFFireNet.  Batch-sum
     accumulators are per (step, layer) and zeroed once per call.  Inputs: eng, T, x_0..x_{T-1},
     initial states (L), parameters; outputs: flow_0..flow_{T-1}, final states (L)."""
 
@@ -1382,9 +1463,16 @@ class FireNetSequence(torch.autograd.Function):
         # step t+1's recurrent dgrad (spike half; membrane half zero-filled) for the others
         g_into = [None] * T   # g_into[t][l]: dL/d state_t[l]
         g_into[T - 1] = [as_nhwc_state(g) if g is not None else None for g in g_final]
+        # the chained schedule (C = 8, fused weight gradients, cells that detach the reset: no membrane
+        # gradient through the state): the spike gradient of a chained layer at steps t >= 1 passes from
+        # task (r, t) to task (r+1, t-1) inside a block and has no buffer
+        chained = bool(eng.bwd_chain) and C == 8 and bool(ctx.fuse) and L <= _lib.MAX_CHAIN_TASKS
+        chain = ([r for r in chainable_layers(eng.rec)
+                  if getattr(eng.cells[r], "detach", True) and getattr(eng.cells[r + 1], "detach", True)]
+                 if chained else [])
         g_out = [None] * T    # g_out[t][l]: dL/d (state input of step t)[l], written by step t's backward
         for t in range(T - 1, 0, -1):
-            g_out[t] = [empty_state(B, C, H, W, dev) if eng.rec[l] else None for l in range(L)]
+            g_out[t] = [empty_state(B, C, H, W, dev) if (eng.rec[l] and l not in chain) else None for l in range(L)]
             g_into[t - 1] = g_out[t]
         g0 = [None] * L
         for l in range(L):
@@ -1419,21 +1507,27 @@ class FireNetSequence(torch.autograd.Function):
                                 (gcur, bnc, ys, stats, ctx.bits), (bptr[t], bptr[t - 1] if t >= 1 else [None] * L)))
             eng.pending_layers.append(tuple(l for l in range(L) if not ((fuse and l > 0) or (fuse_head and l == 0))))
         try:
+            # wavefront launches (the chained schedule's are described at chained_bwd_slots):
             # backward kernel j of step t: j = 0 top (pred + LIF of layer L-1), j >= 1 layer L-j;
             # in reversed time tau = T-1-t the dependencies have the forward's shape: (j-1, tau)
             # (the BN-backward sums of layer L-j), (j, tau-1) (the membrane gradient from step t+1),
             # and (j+1, tau-1) where layer L-j-1 is recurrent (its spikes' gradient from the
             # recurrent dgrad of step t+1)
-            for tasks in wavefront_slots(T, L + 1):
-                layers, top = [], None
-                for j, tau in tasks:
-                    t = T - 1 - tau
+            if chained:
+                # tasks (l, t, first half of a chained pair): layer l, or l = L the top task
+                launches = [[(l, t, len(node) == 2 and i == 0) for node in la for i, (l, t) in enumerate(node)]
+                            for la in chained_bwd_slots(T, eng.rec, chain)]
+            else:
+                launches = [[(L - j, T - 1 - tau, False) for j, tau in tasks] for tasks in wavefront_slots(T, L + 1)]
+            for launch in launches:
+                layers, pairs, top = [], [], None
+                for l, t, first_half in launch:
                     acc = 0 if (fresh and t == T - 1) else 1
-                    if j == 0:
+                    if l == L:
                         top = _bwd_top_args(eng, B, H, W, ys[t], stats[t], mem_in[t], neurons, g_into[t], gfl[t],
                                             flows[t], gcur[t], gmem[t], bacc[t])
                     else:
-                        l = L - j
+                        pairs.append(1 if first_half else 0)
                         a = _bwd_layer_args(eng, l, B, H, W, cin0, ys[t], stats[t], mem_in[t], neurons,
                                             g_into[t], gcur[t], gmem[t], bacc[t], bnc[t], glayers, gpw, gpb,
                                             acc, wfwd, wbwd, g_out[t], ext[t], gxs[t] if l == 0 else None)
@@ -1458,8 +1552,13 @@ class FireNetSequence(torch.autograd.Function):
                             eng.slab_live[l] = True
                         layers.append(a)
                 arr = (_lib.LayerBwdArgs * max(len(layers), 1))(*layers)
-                _lib.call("bwd_slot", lib.snnflow_bwd_slot, arr, len(layers),
-                          ctypes.byref(top) if top is not None else None, s)
+                if chained:
+                    _lib.call("bwd_slot", lib.snnflow_bwd_chain, arr, len(layers),
+                              (ctypes.c_ubyte * max(len(pairs), 1))(*pairs),
+                              ctypes.byref(top) if top is not None else None, s)
+                else:
+                    _lib.call("bwd_slot", lib.snnflow_bwd_slot, arr, len(layers),
+                              ctypes.byref(top) if top is not None else None, s)
             _lib.timer_close()
             for l in range(L):
                 for t in range(T):

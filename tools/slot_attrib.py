@@ -1,6 +1,6 @@
 """Per-task-kind attribution of the C = 8 wavefront slot launches from per-dispatch rocprofv3 data.
 
-    python tools/slot_attrib.py <counter_collection.csv | kernel_trace.csv> [fwd|bwd] [T] > out.json
+    python tools/slot_attrib.py <counter_collection.csv | kernel_trace.csv> [fwd|bwd|bwdchain] [T] > out.json
 
 Every slot launch of a LIFFireNet window holds a known mix of layer-steps (task (k, t) in launch
 k + 2t, engine.wavefront_slots), so a per-dispatch quantity -- a PMC counter, or the duration from a
@@ -13,6 +13,8 @@ Task kinds, backward (launch d: j + 2 tau = d, j = 0 top, j >= 1 layer L - j, st
   top (pred + LIF backward of layer 6), ff (LIF-fed feed-forward layer with its fused weight
   gradient), rec (recurrent layer, t >= 1: packed dW_ff | dW_rec), rec0 (recurrent layer at t = 0:
   no s_prev), head (layer 0: one block).
+bwdchain: the chained backward schedule (engine.chained_bwd_slots, T + L launches): the same kinds plus
+  pair (the recurrent task (r, t+1) and the feed-forward task (r+1, t) in one block per tile).
 Forward (launch d: k + 2t = d): head (conv of the event counts), ff (LIF of layer k-1 + conv k),
 rec (the same + the recurrent conv), top (LIF of layer 6 + pred).
 """
@@ -27,7 +29,36 @@ from scipy.optimize import nnls
 L, REC = 7, (1, 4)
 
 
+def mix_chain(T):
+    import os
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))),
+                                    "snn_event-based_optical_flow_amd"))
+    from snnflow.engine import chained_bwd_slots
+
+    kinds = ["top", "ff", "rec", "rec0", "head", "pair"]
+    rec = [l in REC for l in range(L)]
+    rows = []
+    for launch in chained_bwd_slots(T, rec, REC):
+        v = dict.fromkeys(kinds, 0)
+        for node in launch:
+            (k, t) = node[0]
+            if len(node) == 2:
+                v["pair"] += 1
+            elif k == L:
+                v["top"] += 1
+            elif k == 0:
+                v["head"] += 1
+            elif k in REC:
+                v["rec" if t >= 1 else "rec0"] += 1
+            else:
+                v["ff"] += 1
+        rows.append([v[x] for x in kinds])
+    return kinds, np.array(rows, dtype=np.float64)
+
+
 def mix(direction, T):
+    if direction == "bwdchain":
+        return mix_chain(T)
     K = L + 1
     kinds = ["top", "ff", "rec", "rec0", "head"] if direction == "bwd" else ["head", "ff", "rec", "top"]
     rows = []
@@ -83,7 +114,8 @@ def main():
     kinds, A1 = mix(direction, T)
     n = A1.shape[0]
     vals = {}
-    for kname in (f"k_{direction}_slot<8>(", f"k_{direction}_slot_t8(", f"k_{direction}_slot_p8("):
+    kdir = "bwd" if direction == "bwdchain" else direction
+    for kname in (f"k_{kdir}_slot<8>(", f"k_{kdir}_slot_t8(", f"k_{kdir}_slot_p8("):
         vals = dispatch_values(path, kname)  # (the C = 8 slot kernel the run launched)
         if vals:
             break
