@@ -281,6 +281,21 @@ int snnflow_slot_supported(int c, int cin0);
 #define SNNFLOW_MAX_CHAIN_TASKS 7
 int snnflow_bwd_chain(const snnflow_layer_bwd_args* layer, int nlayer, const unsigned char* pair,
                       const snnflow_lif_bwd_args* lif, void* stream);
+/* Forward launch with chained pairs (additive; the ABI version is unchanged).  Up to
+ * SNNFLOW_MAX_CHAIN_TASKS conv tasks and the optional top task, under snnflow_fwd_slot's rules, plus:
+ * pair (NULL: none; else nconv flags) marks with pair[i] != 0 that tasks i and i + 1 are a chained pair.
+ * The task of layer r+1 at step t-1 computes the spikes of a recurrent layer r on each tile's halo, which
+ * are the recurrent input of the task of layer r at step t on the same tile, so one block per tile runs
+ * the first task and then the second and hands the spikes over in LDS: the two-launch loop around a
+ * recurrent layer becomes one launch per step.  A pair is (c = cin = 8 feed-forward LIF-fed task,
+ * c = cin = 8 recurrent LIF-fed task) of equal shape, both eligible for the forward tile pipeline
+ * (snnflow_set_pipe > 0, no spike bit planes, tensors under 2^31 bytes); the first task's layer l-1
+ * (prev, prev_y, prev_state) is the second task's own layer one step earlier.  The hand-over replaces the
+ * second task's s_prev load: the field must be NULL.  Everything else each task does is what it does
+ * alone (the first still stores the spike half of prev_state unless state_spk_skip).  Malformed pairs are
+ * refused before anything is launched. */
+int snnflow_fwd_chain(const snnflow_conv_fwd_args* conv, int nconv, const unsigned char* pair,
+                      const snnflow_lif_fwd_args* lif, void* stream);
 /* Tuning (ABI 27): tiles per block of the c = 8 LIF-fed forward tasks of the wavefront launches
  * (0: one tile per block; >= 1: the tile pipeline, which overlaps the next tile's halo loads by
  * LDS-DMA with this tile's math).  Process-wide; default from SNNFLOW_PIPE_FWD at load time.  Results

@@ -3271,15 +3271,24 @@ enum SlotKind : int {
     SK_LIF, SK_LIF_REC,                      // LIF(l-1) on the halo + conv(l) [+ rec]
     SK_TOP, SK_TOP_PRED,                     // LIF of the last layer [+ pred]
     SK_LIF_P, SK_LIF_REC_P,                  // C = 8 forward SK_LIF / SK_LIF_REC as a tile pipeline (fwd_lif8_pipe)
-    SK_CHAIN                                 // C = 8 backward: SK_LIF_REC of (l, t+1), then SK_LIF of (l+1, t), one block per tile
+    SK_CHAIN,                                // C = 8 backward: SK_LIF_REC of (l, t+1), then SK_LIF of (l+1, t), one block per tile
+    SK_FCHAIN                                // C = 8 forward: SK_LIF_P of (r+1, t-1), then SK_LIF_REC_P of (r, t), one block per tile (fwd_chain8_pipe)
 };
 
+// Forward launches carry up to kFwdTasks conv tasks (snnflow_fwd_chain; snnflow_fwd_slot keeps its
+// kSlotTasks) in up to kFwdNodes block ranges: a range runs one task, or the two consecutive tasks of a
+// chained pair (SK_FCHAIN).
+constexpr int kFwdTasks = SNNFLOW_MAX_CHAIN_TASKS, kFwdNodes = kFwdTasks + 1;
 struct FwdSlotParams {
-    snnflow_conv_fwd_args conv[kSlotTasks];
+    snnflow_conv_fwd_args conv[kFwdTasks];
     snnflow_lif_fwd_args lif;
-    int kind[kSlotTasks], blk0[kSlotTasks], nblk[kSlotTasks];
-    int ntask;
+    // per block range: kind, first block, blocks.  conv[k] is the (first) task of range k (no index to
+    // fetch before a task's arguments can be) and conv[second[k]] the second task of a chained pair
+    // (stored behind the ranges' own tasks; read after the first half's prologue has begun)
+    int kind[kFwdNodes], blk0[kFwdNodes], nblk[kFwdNodes], second[kFwdNodes];
+    int ntask;  // block ranges
 };
+static_assert(sizeof(FwdSlotParams) + 256 <= 4096, "kernel arguments: 4 KB with the hidden ones");
 // Backward launches carry up to kBwdTasks layer tasks in up to kBwdNodes block ranges (a range runs one
 // task, or the two consecutive tasks of a chained pair: SK_CHAIN), which as public structs would pass
 // HIP's 4 KB of kernel arguments (which the 256 B of hidden arguments share).  The device-side record
@@ -3341,11 +3350,13 @@ struct PipeFwdLds {
     static constexpr int FLOATS = BYTES / 4;
 };
 
+constexpr int kChainFwdFloats = (2 * kPipeRaw + 2 * kPipeSpk + 2 * kPipeFrag) / 4;  // ChainFwdLds (fwd_chain8_pipe)
 template <int C>
 struct SlotLds {
     static constexpr int FWD_ALL = cmax(cmax(ConvFwdLds<1, C, false, false, 2>::FLOATS, ConvFwdLds<5, C, false, false, 2>::FLOATS),
                                         cmax(ConvFwdLds<C, C, false, false, 2>::FLOATS, ConvFwdLds<C, C, false, true, 2>::FLOATS));
-    static constexpr int FWD_P = C == 8 ? PipeFwdLds<true>::FLOATS : 0;  // the tile pipeline (C = 8)
+    // the tile pipeline and the chained pair (C = 8)
+    static constexpr int FWD_P = C == 8 ? cmax(PipeFwdLds<true>::FLOATS, kChainFwdFloats) : 0;
     static constexpr int FWD = cmax(cmax(cmax(kSlotAllKinds<C> ? FWD_ALL : 0, kLifQFwdLds<C>), FWD_P),
                                     cmax(cmax(ConvFwdLds<2, C, false, false, 2>::FLOATS, ConvFwdLds<4, C, false, false, 2>::FLOATS),
                                          cmax(ConvFwdLds<C, C, true, false, 2>::FLOATS, ConvFwdLds<C, C, true, true, 2>::FLOATS)));
@@ -3774,13 +3785,302 @@ __device__ void fwd_lif8_pipe(const snnflow_conv_fwd_args& a, const Grid g, floa
     }
 }
 
+// ---------------------------------------------------------------------------
+// A chained forward pair (slot kind SK_FCHAIN): one block per tile runs task A = F(r+1, t-1) and then
+// task B = F(r, t), r a recurrent LIF-fed layer and r+1 a feed-forward layer below the top.  A's LIF of
+// layer r computes the spikes s_r(t-1) on the tile's halo as a bf16 tile in LDS for its own conv; that
+// tile is exactly B's recurrent input (out-of-image pixels zero in both), so B takes it from LDS instead
+// of reading the spike half of the state back as s_prev: the edge F(r+1, t-1) -> F(r, t), which made the
+// loop around a recurrent layer cost two launches per step, stays inside the block.  LIF output is 0/1,
+// so B's recurrent conv always runs on the matrix cores (no exactness test, no s_prev registers).
+// Organised like fwd_lif8_pipe; per tile:
+//   wait(DMA A) + barrier -> LIF of layer r over the halo (state r at t-1, spikes into RSPK) -> barrier
+//   -> DMA B into the raw regions -> conv r+1 on RSPK, store y_{r+1}(t-1) -> wait(DMA B) + barrier
+//   -> LIF of layer r-1 (state r-1 at t, spikes into SPK) -> barrier -> DMA A of the next tile
+//   -> conv r on SPK + recurrent conv r on RSPK, store y_r(t).
+// Every DMA has an MFMA phase over it; RSPK is rewritten only after the next tile's first barrier.
+// Each half runs its own per-block prologue and issues its own batch-sum atomics; each half's arithmetic
+// and its tiles per block are those of the task on its own (fwd_lif8_pipe).
+// ---------------------------------------------------------------------------
+// LDS: 46,464 B of regions.  The pool holds the raw halos, both spike tiles and the two feed-forward
+// fragment sets (PipeFwdLds<true>'s size); the recurrent fragments, the LIF coefficients of both halves
+// and the gathered batch sums live in the block-sum scratch (sum_scratch), which every body uses only
+// for its final batch sums -- here after a barrier that ends the last tile's reads of the fragments --
+// so the pair adds nothing to the kernel's LDS.
+struct ChainFwdLds {
+    static constexpr int RAWY = 0, RAWM = kPipeRaw, SPK = 2 * kPipeRaw, RSPK = SPK + kPipeSpk;
+    static constexpr int FA = RSPK + kPipeSpk, FB = FA + kPipeFrag;  // ff(r+1), ff(r)
+    static constexpr int BYTES = FB + kPipeFrag;
+    static constexpr int FLOATS = BYTES / 4;
+    // in sum_scratch (bytes): rec(r) fragments, LifCoef[2][8], double sums[16]
+    static constexpr int X_FR = 0, X_COEF = kPipeFrag, X_SUMS = X_COEF + 2 * 8 * 16, X_BYTES = X_SUMS + 16 * 8;
+};
+static_assert(ChainFwdLds::BYTES + kPipeFrag == 46464 && ChainFwdLds::FLOATS == kChainFwdFloats, "chained forward pair: LDS budget");
+static_assert(ChainFwdLds::X_BYTES <= kSumScratch * 4 && sizeof(LifCoef) == 16 && ChainFwdLds::X_SUMS % 8 == 0,
+              "chained forward pair: fragments, coefficients and sums in the block-sum scratch");
+
+// The raw halo of tile t by LDS-DMA (fwd_lif8_pipe's issue): 11 wave-loads of 64 x 16 B per tensor,
+// wave w issues loads w, w + 8, w + 16.
+__device__ inline void chain_issue(const __amdgpu_buffer_rsrc_t rs_y, const __amdgpu_buffer_rsrc_t rs_m, bool has_mem,
+                                   char* lds, const Tile& t, int H, int W, int wv, int lane) {
+    constexpr int C = 8;
+    using L = ChainFwdLds;
+    const int base = ((t.b * H + t.h0 - 1) * W + (t.w0 - 1)) * (C * 4);
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+        const int k = wv + 8 * j;
+        if (k >= 22) break;
+        const bool mem = k >= 11;
+        if (mem && !has_mem) continue;
+        const int kk = mem ? k - 11 : k, ee = kk * 64 + lane, p = ee >> 1, r = p / HWD, cc = p - r * HWD;
+        const bool ok = in_image(t.h0 + r - 1, t.w0 + cc - 1, H, W);
+        const uint32_t off = ok ? (uint32_t)(base + (r * W + cc) * (C * 4) + (ee & 1) * 16) : 0x80000000u;
+        if (ee < 2 * HN)  // the last wave-load is partial: inactive lanes write no LDS
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(mem ? rs_m : rs_y, (lds_void*)(lds + (mem ? L::RAWM : L::RAWY) + kk * 1024),
+                                                     16, off, 0, 0, 0);
+    }
+}
+
+// What the tile loop needs of one half's task (the rest of its arguments is read by its prologue only:
+// both structs whole would not fit the scalar registers).
+struct ChainHalf {
+    __amdgpu_buffer_rsrc_t rs_y, rs_m;  // prev_y, prev_mem (prev_y again where there is none)
+    float4* st4;                        // prev_state
+    float* y;
+    bool has_mem, zr, spk_skip;
+};
+
+// LIF of the task's previous layer over the halo from the raw regions (fwd_lif8_pipe's): the state of
+// the tile's own pixels to prev_state, the spikes as a bf16 tile to `spk`.
+__device__ inline void chain_lif(const ChainHalf& a, int B, int H, int W, const LifCoef* coef, const char* lds, __bf16* spk,
+                                 const Tile& tl, int tid) {
+    constexpr int C = 8, NTB = 2 * NT, R = Halo4<C, NTB>::R;
+    using L = ChainFwdLds;
+    const int qt = tid & 1;
+    const bool has_mem = a.has_mem, zr = a.zr, spk_skip = a.spk_skip;
+    const int64_t plane4 = (int64_t)B * H * W * 2;
+    float4* st4 = a.st4;
+    const LifCoef kc[4] = {coef[4 * qt], coef[4 * qt + 1], coef[4 * qt + 2], coef[4 * qt + 3]};
+#pragma unroll
+    for (int i = 0; i < R; ++i) {
+        const int e = tid + i * NTB;
+        if (e < 2 * HN) {
+            const int p = e >> 1, r = p / HWD, cc = p - r * HWD;
+            const int h = tl.h0 + r - 1, w = tl.w0 + cc - 1;
+            const float4 yv = *reinterpret_cast<const float4*>(lds + L::RAWY + e * 16);
+            const float4 mv = has_mem ? *reinterpret_cast<const float4*>(lds + L::RAWM + e * 16) : make_float4(0.f, 0.f, 0.f, 0.f);
+            float4 sv = make_float4(0.f, 0.f, 0.f, 0.f);
+            if (in_image(h, w, H, W)) {
+                const Lif4 o = zr ? lif_step4(yv, mv, kc, true) : lif_step4(yv, mv, kc, false);
+                sv = o.s;
+                if (r >= 1 && r <= TH && cc >= 1 && cc <= TW) {
+                    const int64_t q = (((int64_t)tl.b * H + h) * W + w) * 2 + qt;
+                    st_state4(st4, q, o.mout);
+                    if (!spk_skip) st_state4(st4, plane4 + q, o.s);
+                }
+            }
+            typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
+            *reinterpret_cast<bf16x4*>(spk + p * 8 + 4 * qt) = bf16x4{(__bf16)sv.x, (__bf16)sv.y, (__bf16)sv.z, (__bf16)sv.w};
+        }
+    }
+}
+
+// Swapped-operand conv of this wave's tile row (fwd_lif8_pipe's): A = fragments (rows co), B = spikes
+// (columns: pixels); rec adds the recurrent conv on rspk.  Returns the lane's four pre-BN currents: lane ->
+// (M-tile lane >> 5, pixel column lane & 15, channel quad (lane >> 4) & 1).
+__device__ inline f32x4 chain_conv(bool rec, const char* ff, const char* fr, const __bf16* spk, const __bf16* rspk, int wv,
+                                   int lane) {
+    const int jj = lane & 15, gg = lane >> 4;
+    const bf16x8* fff = reinterpret_cast<const bf16x8*>(ff) + gg * 8 + (jj & 7);
+    const bf16x8* ffr = reinterpret_cast<const bf16x8*>(fr) + gg * 8 + (jj & 7);
+    f32x4 af[2] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}}, ar[2] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
+#pragma unroll
+    for (int ch = 0; ch < 3; ++ch) {
+        const int tap = 4 * ch + gg, ky = tap / 3, kx = tap - 3 * ky;
+        const bf16x8 fh = fff[ch * 96], fm = fff[ch * 96 + 32], fl = fff[ch * 96 + 64];
+#pragma unroll
+        for (int mt = 0; mt < 2; ++mt) {
+            const int off = ((wv + ky) * HWD + mt * 16 + jj + kx) * 8;
+            bf16x8 b = {};
+            if (tap < 9) b = *reinterpret_cast<const bf16x8*>(spk + off);
+            af[mt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fl, b, af[mt], 0, 0, 0);
+            af[mt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fm, b, af[mt], 0, 0, 0);
+            af[mt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fh, b, af[mt], 0, 0, 0);
+        }
+        if (rec) {
+            const bf16x8 rh = ffr[ch * 96], rm = ffr[ch * 96 + 32], rl = ffr[ch * 96 + 64];
+#pragma unroll
+            for (int mt = 0; mt < 2; ++mt) {
+                const int off = ((wv + ky) * HWD + mt * 16 + jj + kx) * 8;
+                bf16x8 b = {};
+                if (tap < 9) b = *reinterpret_cast<const bf16x8*>(rspk + off);
+                ar[mt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(rl, b, ar[mt], 0, 0, 0);
+                ar[mt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(rm, b, ar[mt], 0, 0, 0);
+                ar[mt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(rh, b, ar[mt], 0, 0, 0);
+            }
+        }
+    }
+    f32x4 yv;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        const float y0 = rec ? af[0][r] + ar[0][r] : af[0][r];  // ff + rec
+        const float y1 = rec ? af[1][r] + ar[1][r] : af[1][r];
+        const auto sw = __builtin_amdgcn_permlane32_swap(__builtin_bit_cast(unsigned, y0), __builtin_bit_cast(unsigned, y1),
+                                                         false, false);
+        yv[r] = __builtin_bit_cast(float, sw[0]);
+    }
+    return yv;
+}
+
+// Batch sums of the block's tiles (fwd_lif8_pipe's): 16-lane rows by DPP, rows and waves through LDS,
+// fp64 atomics.  Called by every thread of the block (one barrier).
+__device__ inline void chain_batch_sums(double* acc, const Grid& g, const float (&bs)[4], const float (&bq)[4]) {
+    constexpr int C = 8;
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    float v[8] = {bs[0], bs[1], bs[2], bs[3], bq[0], bq[1], bq[2], bq[3]};
+#pragma unroll
+    for (int j = 0; j < 8; ++j) v[j] += dppf<0xB1>(v[j]);
+#pragma unroll
+    for (int j = 0; j < 8; ++j) v[j] += dppf<0x4E>(v[j]);
+#pragma unroll
+    for (int j = 0; j < 8; ++j) v[j] += dppf<0x141>(v[j]);
+#pragma unroll
+    for (int j = 0; j < 8; ++j) v[j] += dppf<0x140>(v[j]);
+    float(*red)[4][8] = reinterpret_cast<float(*)[4][8]>(sum_scratch());  // [wave][16-lane row][8 sums]
+    if ((lane & 15) == 0) {
+#pragma unroll
+        for (int j = 0; j < 8; ++j) red[wv][lane >> 4][j] = v[j];
+    }
+    __syncthreads();
+    if (acc && tid < 2 * C) {  // sum (tid < 8) or sum of squares of channel c
+        const int c = tid & 7, sq = tid >> 3, qd = c >> 2, j = sq * 4 + (c & 3);
+        double s = 0.0;
+#pragma unroll
+        for (int w = 0; w < 8; ++w) s += (double)red[w][qd][j] + (double)red[w][qd + 2][j];
+        atomicAdd(acc_shard(acc, 2 * C, g.bid) + sq * C + c, s);
+    }
+}
+
+// pa: task A = F(r+1, t-1) (feed-forward), pb: task B = F(r, t) (recurrent; its s_prev is the hand-over),
+// both in the kernel-argument segment: each half's struct is built for its prologue only.
+typedef const __attribute__((address_space(4))) snnflow_conv_fwd_args* conv_karg;
+__device__ void fwd_chain8_pipe(const conv_karg pa, const conv_karg pb, const Grid g, float* pool) {
+    constexpr int C = 8;
+    using L = ChainFwdLds;
+    char* const lds = reinterpret_cast<char*>(pool);
+    char* const xlds = reinterpret_cast<char*>(sum_scratch());
+    LifCoef(*coef)[C] = reinterpret_cast<LifCoef(*)[C]>(xlds + L::X_COEF);  // of layer r (A's LIF), of layer r-1 (B's LIF)
+    double* const sums = reinterpret_cast<double*>(xlds + L::X_SUMS);
+    const int lane0 = threadIdx.x & 63;
+    const int wv = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);
+    const int B = pa->B, H = pa->H, W = pa->W, ntiles = B * tiles_per_image(H, W);
+    int v_cur = g.bid < ntiles ? g.bid : -1;  // tiles v = bid, bid + nb, ...
+    if (v_cur < 0) return;
+    const bool lead = g.bid == 0;
+    const uint32_t nbytes = (uint32_t)B * H * W * C * 4;  // < 2^31 (host check)
+    Tile tl = block_tile(H, W, Grid{v_cur, ntiles});
+
+    // ---- prologue (once per block), each half's own: batch-sum shards, neuron parameters, running
+    // statistics, consumed accumulators, fragments (B's shard loads are in flight over A's prologue)
+    const bool train_a = pa->prev.bn_train != 0, train_b = pb->prev.bn_train != 0;
+    AccGather<2 * C> gat_a, gat_b;
+    if (train_a) acc_gather_load<2 * C>(as_global_ptr(pa->prev_acc), 2 * C, gat_a);
+    if (train_b) acc_gather_load<2 * C>(as_global_ptr(pb->prev_acc), 2 * C, gat_b);
+    ChainHalf ha, hb;
+    auto prologue = [&](const snnflow_conv_fwd_args& t, const AccGather<2 * C>& gat, LifCoef* cf, ChainHalf& hf, char* frag,
+                        bool first) {
+        const NeuronRegs nr = load_neuron(t.prev, C, lead);
+        FragC8 fz, fzr;
+        fz.load(t.wt_ff_t);
+        if (!first) fzr.load(t.wt_rec_t);
+        hf.has_mem = t.prev_mem != nullptr;
+        hf.zr = t.prev.zero_reset != 0;
+        hf.spk_skip = t.state_spk_skip != 0;
+        hf.st4 = reinterpret_cast<float4*>(t.prev_state);
+        hf.y = t.y;
+        hf.rs_y = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(t.prev_y), (short)0, (int)nbytes, 0x00020000);
+        hf.rs_m = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(hf.has_mem ? t.prev_mem : t.prev_y), (short)0, (int)nbytes,
+                                                    0x00020000);
+        if (first) chain_issue(hf.rs_y, hf.rs_m, hf.has_mem, lds, tl, H, W, wv, lane0);
+        // (the barrier inside the second half's reduce orders the first half's reads of sums before its writes)
+        if (t.prev.bn_train) acc_gather_reduce<2 * C>(gat, sums);
+        lif_prologue(t.prev, nr, sums, C, (double)B * H * W, t.prev_stats, cf, nullptr, lead);
+        fz.store(reinterpret_cast<__bf16*>(frag));
+        if (!first) fzr.store(reinterpret_cast<__bf16*>(xlds + L::X_FR));
+        zero_consumed(t.zero0, t.zero1, t.zero_n, g);
+    };
+    {
+        const snnflow_conv_fwd_args a = task_args(pa);
+        prologue(a, gat_a, coef[0], ha, lds + L::FA, true);
+    }
+    {
+        const snnflow_conv_fwd_args b = task_args(pb);
+        prologue(b, gat_b, coef[1], hb, lds + L::FB, false);
+    }
+
+    float sa[4] = {0.f, 0.f, 0.f, 0.f}, qa[4] = {0.f, 0.f, 0.f, 0.f};  // this lane's batch sums of A
+    float sb[4] = {0.f, 0.f, 0.f, 0.f}, qb[4] = {0.f, 0.f, 0.f, 0.f};  // and of B
+    __bf16* const spk = reinterpret_cast<__bf16*>(lds + L::SPK);
+    __bf16* const rspk = reinterpret_cast<__bf16*>(lds + L::RSPK);
+
+    // One copy of the tile phases, run as half A and then half B of every tile (second = 0, 1) with that
+    // half's parameters: two inlined copies would double the body's code for nothing.
+    Tile cur = tl;
+    for (int second = 0; v_cur >= 0; second ^= 1) {
+        const ChainHalf hf = second ? hb : ha;
+        vm_wait<0>();     // this wave's DMA of this half (and its stores of the half before)
+        __syncthreads();  // every wave's DMA landed; every wave is done with the spike tile this half rewrites
+        // (the lane's tile-independent index math is redone per phase from an opaque copy of the thread
+        // index: hoisted out of the loop it holds ~30 registers, see fwd_lif8_pipe)
+        chain_lif(hf, B, H, W, coef[second], lds, second ? spk : rspk, cur, opaque_int(threadIdx.x));
+        __syncthreads();  // raw halos free, this half's spike tile complete
+        // the raw halo of the next half: B's of this tile, or A's of the block's next tile
+        int v_nxt = v_cur;
+        if (second) {
+            v_nxt = v_cur + g.nb < ntiles ? v_cur + g.nb : -1;
+            if (v_nxt >= 0) tl = block_tile(H, W, Grid{v_nxt, ntiles});
+        }
+        if (v_nxt >= 0) {
+            const ChainHalf hn = second ? ha : hb;
+            chain_issue(hn.rs_y, hn.rs_m, hn.has_mem, lds, tl, H, W, wv, opaque_int(threadIdx.x) & 63);
+        }
+        const int lane = opaque_int(threadIdx.x) & 63;
+        const f32x4 yv = chain_conv(second != 0, lds + (second ? L::FB : L::FA), xlds + L::X_FR, second ? spk : rspk, rspk, wv, lane);
+        const int qd = (lane >> 4) & 1, h = cur.h0 + wv, w = cur.w0 + (lane >> 5) * 16 + (lane & 15);
+        if (h < H && w < W) {
+            *reinterpret_cast<float4*>(hf.y + (((int64_t)cur.b * H + h) * W + w) * C + 4 * qd) =
+                make_float4(yv[0], yv[1], yv[2], yv[3]);
+            if (second) {
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    sb[r] += yv[r];
+                    qb[r] += yv[r] * yv[r];
+                }
+            } else {
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    sa[r] += yv[r];
+                    qa[r] += yv[r] * yv[r];
+                }
+            }
+        }
+        v_cur = v_nxt;
+        cur = tl;
+    }
+
+    __syncthreads();  // the last tile's reads of the recurrent fragments: the scratch is free for the block sums
+    chain_batch_sums(as_global_ptr(pa->acc), g, sa, qa);
+    __syncthreads();  // the scratch of the first set is read
+    chain_batch_sums(as_global_ptr(pb->acc), g, sb, qb);
+}
+
 template <int C>
 __global__ __launch_bounds__(NT * 2, C == 8 ? 6 : 1) void k_fwd_slot(FwdSlotParams) {
     typedef const __attribute__((address_space(4))) FwdSlotParams* cptr;
     const cptr pp = (cptr)__builtin_amdgcn_kernarg_segment_ptr();
     Grid g;
-    const int k = slot_task(pp, g);
-    if (g.bid >= g.nb) return;  // padding block of a range
+    const int k = slot_task<kFwdNodes>(pp, g);
+    if (g.bid >= g.nb) return;  // padding block of a range (a chained pair's skips both halves)
     __shared__ __attribute__((aligned(16))) float pool[SlotLds<C>::FWD];
     switch (pp->kind[k]) {
 #define FWD_CONV(ALL, KIND, ...)                              \
@@ -3808,6 +4108,12 @@ __global__ __launch_bounds__(NT * 2, C == 8 ? 6 : 1) void k_fwd_slot(FwdSlotPara
                     if (pp->kind[k] == SK_LIF_REC_P) fwd_lif8_pipe<true>(a, g, pool);
                     else fwd_lif8_pipe<false>(a, g, pool);
                 }
+            }
+            break;
+        }
+        case SK_FCHAIN: {
+            if constexpr (C == 8) {
+                fwd_chain8_pipe(&pp->conv[k], &pp->conv[pp->second[k]], g, pool);
             }
             break;
         }
@@ -4451,7 +4757,7 @@ static bool slot_c(int c) { return c == 8 || c == 16 || c == 32; }
 #endif
 static int slot_rank(int kind) {
     switch (kind) {
-        case SK_LIF_REC_P: case SK_LIF_P: return 0;
+        case SK_LIF_REC_P: case SK_LIF_P: case SK_FCHAIN: return 0;
         case SK_LIF_REC: case SK_PLAIN_REC: return 0;
         case SK_LIF: case SK_PLAIN: return 1;
         default: return 2;
@@ -4513,10 +4819,21 @@ static int slot_ranges(const int* nblk, int n, int* blk0) {
     return b;
 }
 
-int snnflow_fwd_slot(const snnflow_conv_fwd_args* conv, int nconv, const snnflow_lif_fwd_args* lif, void* stream) {
-    const int nt = nconv + (lif ? 1 : 0);
-    if (nconv < 0 || nt <= 0 || nt > kSlotTasks || (nconv && !conv)) SNN_FAIL(SNNFLOW_E_ARG, "fwd_slot: task count");
+// Block order of the chained pairs of a forward launch: 0 layer order, 1 pairs first, 2 pairs last (A/B)
+static int g_fchain_order = env_int("SNNFLOW_FCHAIN_ORDER", 1);
+
+// Can conv task a run as a pipelined task (fwd_lif8_pipe, or one half of a chained pair)?
+static bool pipe_task(const snnflow_conv_fwd_args& a) {
+    return a.c == 8 && a.cin == 8 && a.lif_in && g_pipe_fwd > 0 && pipe_fits(a.B, a.H, a.W, a.c) && !a.prev_spk_bits &&
+           !a.s_prev_bits;  // (the tile pipeline reads and writes fp32 spike planes only)
+}
+
+// One forward launch: the conv tasks in order, pair[i] != 0 chaining task i (feed-forward, (r+1, t-1)) to
+// task i + 1 (recurrent, (r, t)) in one block range (validated by snnflow_fwd_chain), then the top task.
+static int fwd_launch(const snnflow_conv_fwd_args* conv, int nconv, const unsigned char* pair,
+                      const snnflow_lif_fwd_args* lif, void* stream) {
     FwdSlotParams p = {};
+    int taskkind[kFwdTasks], taskblk[kFwdTasks], first[kFwdNodes];  // first[k]: (first) task of block range k
     const int c = nconv ? conv[0].c : lif->c;
     const int B = nconv ? conv[0].B : lif->B, H = nconv ? conv[0].H : lif->H, W = nconv ? conv[0].W : lif->W;
     if (!slot_c(c)) SNN_FAIL(SNNFLOW_E_CHANNELS, "fwd_slot: c must be 8, 16 or 32");
@@ -4540,19 +4857,27 @@ int snnflow_fwd_slot(const snnflow_conv_fwd_args* conv, int nconv, const snnflow
         }
         if (c != 8 && !(kind == SK_HEAD2 || kind == SK_HEAD4 || kind == SK_LIF || kind == SK_LIF_REC))
             SNN_FAIL(SNNFLOW_E_CHANNELS, "fwd_slot: c = 16 / 32 runs the LIFFireNet task kinds only");
-        p.conv[i] = a;
-        p.nblk[i] = snnflow_conv_blocks(B, H, W);
-        if (c == 8 && g_pipe_fwd > 0 && (kind == SK_LIF || kind == SK_LIF_REC) && pipe_fits(B, H, W, c) &&
-            !a.prev_spk_bits && !a.s_prev_bits)  // (the tile pipeline reads and writes fp32 spike planes only)
-            kind = kind == SK_LIF ? SK_LIF_P : SK_LIF_REC_P;
-        p.kind[i] = kind;
+        taskblk[i] = snnflow_conv_blocks(B, H, W);
+        if ((kind == SK_LIF || kind == SK_LIF_REC) && pipe_task(a)) kind = kind == SK_LIF ? SK_LIF_P : SK_LIF_REC_P;
+        taskkind[i] = kind;
     }
     const int tpb = g_pipe_fwd;
     for (int i = 0; i < nconv; ++i) {
-        if (p.kind[i] != SK_LIF_P && p.kind[i] != SK_LIF_REC_P) continue;
-        const int nt = p.nblk[i];
-        p.nblk[i] = pipe_blocks(nt, tpb);
-        if (p.nblk[i] > (nt + 7) / 8 * 8) p.nblk[i] = (nt + 7) / 8 * 8;
+        if (taskkind[i] != SK_LIF_P && taskkind[i] != SK_LIF_REC_P) continue;
+        const int nt = taskblk[i];
+        taskblk[i] = pipe_blocks(nt, tpb);
+        if (taskblk[i] > (nt + 7) / 8 * 8) taskblk[i] = (nt + 7) / 8 * 8;
+    }
+    // block ranges: one per task, one per chained pair (both halves pipelined tasks of one shape: the
+    // blocks and the tiles per block of either alone)
+    int nn = 0;
+    for (int i = 0; i < nconv; ++i) {
+        const bool ch = pair && pair[i];
+        first[nn] = i;
+        p.kind[nn] = ch ? SK_FCHAIN : taskkind[i];
+        p.nblk[nn] = taskblk[i];
+        ++nn;
+        if (ch) ++i;
     }
     if (lif) {
         if (const int e = lif_fwd_check(lif)) return e;
@@ -4560,20 +4885,73 @@ int snnflow_fwd_slot(const snnflow_conv_fwd_args* conv, int nconv, const snnflow
             SNN_FAIL(SNNFLOW_E_ARG, "fwd_slot: tasks of different shapes");
         if (c != 8 && !lif->pred_w) SNN_FAIL(SNNFLOW_E_CHANNELS, "fwd_slot: c = 16 / 32 top task needs the prediction");
         p.lif = *lif;
-        p.kind[nconv] = lif->pred_w ? SK_TOP_PRED : SK_TOP;
-        p.nblk[nconv] = slot_top_blocks(c, B, H, W);
+        p.kind[nn] = lif->pred_w ? SK_TOP_PRED : SK_TOP;
+        p.nblk[nn] = slot_top_blocks(c, B, H, W);
     }
-    if (c != 8) slot_sort(p.conv, p.kind, p.nblk, nconv);
-    else if (SNNFLOW_SLOT_ORDER8) slot_sort(p.conv, p.kind, p.nblk, nconv, SNNFLOW_SLOT_ORDER8 == 2);
-    else if (g_pipe_fwd > 0 && g_pipe_order) slot_sort(p.conv, p.kind, p.nblk, nconv, g_pipe_order == 2);
-    p.ntask = nt;
-    const int nb = slot_ranges(p.nblk, nt, p.blk0);
+    if (c != 8) slot_sort(first, p.kind, p.nblk, nn);
+    else if (SNNFLOW_SLOT_ORDER8) slot_sort(first, p.kind, p.nblk, nn, SNNFLOW_SLOT_ORDER8 == 2);
+    else if (g_pipe_fwd > 0 && g_pipe_order) slot_sort(first, p.kind, p.nblk, nn, g_pipe_order == 2);
+    if (c == 8 && pair && g_fchain_order) {
+        // chained pairs to the launch's first (1) or last (2) block ranges, everything else in the order above
+        const bool last = g_fchain_order == 2;
+        for (int i = 1; i < nn; ++i)
+            for (int j = i; j > 0 && (p.kind[j] == SK_FCHAIN) != last && (p.kind[j - 1] == SK_FCHAIN) == last; --j) {
+                const int tf = first[j]; first[j] = first[j - 1]; first[j - 1] = tf;
+                const int tk = p.kind[j]; p.kind[j] = p.kind[j - 1]; p.kind[j - 1] = tk;
+                const int tn = p.nblk[j]; p.nblk[j] = p.nblk[j - 1]; p.nblk[j - 1] = tn;
+            }
+    }
+    int nsec = nn;  // the ranges' own tasks, then the pairs' second tasks (nn + pairs = nconv)
+    for (int k = 0; k < nn; ++k) {
+        p.conv[k] = conv[first[k]];
+        if (p.kind[k] == SK_FCHAIN) {
+            p.second[k] = nsec;
+            p.conv[nsec++] = conv[first[k] + 1];
+        }
+    }
+    p.ntask = nn + (lif ? 1 : 0);
+    const int nb = slot_ranges(p.nblk, p.ntask, p.blk0);
     const hipStream_t s = (hipStream_t)stream;
     if (c == 8) hipLaunchKernelGGL(k_fwd_slot<8>, dim3(nb), dim3(2 * NT), 0, s, p);
     else if (c == 16) hipLaunchKernelGGL(k_fwd_slot<16>, dim3(nb), dim3(2 * NT), 0, s, p);
     else hipLaunchKernelGGL(k_fwd_slot<32>, dim3(nb), dim3(2 * NT), 0, s, p);
     SNN_CHECK_LAUNCH();
     return 0;
+}
+
+int snnflow_fwd_slot(const snnflow_conv_fwd_args* conv, int nconv, const snnflow_lif_fwd_args* lif, void* stream) {
+    const int nt = nconv + (lif ? 1 : 0);
+    if (nconv < 0 || nt <= 0 || nt > kSlotTasks || (nconv && !conv)) SNN_FAIL(SNNFLOW_E_ARG, "fwd_slot: task count");
+    return fwd_launch(conv, nconv, nullptr, lif, stream);
+}
+
+int snnflow_fwd_chain(const snnflow_conv_fwd_args* conv, int nconv, const unsigned char* pair,
+                      const snnflow_lif_fwd_args* lif, void* stream) {
+    if (nconv < 0 || nconv > kFwdTasks || nconv + (lif ? 1 : 0) <= 0 || (nconv && !conv))
+        SNN_FAIL(SNNFLOW_E_ARG, "fwd_chain: task count");
+    for (int i = 0; pair && i < nconv; ++i) {
+        if (!pair[i]) continue;
+        if (i + 1 >= nconv || pair[i + 1]) SNN_FAIL(SNNFLOW_E_ARG, "fwd_chain: a pair is two consecutive tasks");
+        const snnflow_conv_fwd_args& a = conv[i];      // F(r+1, t-1)
+        const snnflow_conv_fwd_args& b = conv[i + 1];  // F(r, t)
+        if (a.c != 8 || a.cin != 8 || b.c != 8 || b.cin != 8 || !a.lif_in || !b.lif_in)
+            SNN_FAIL(SNNFLOW_E_CHANNELS, "fwd_chain: pairs are c = cin = 8 LIF-fed tasks");
+        if (a.B != b.B || a.H != b.H || a.W != b.W) SNN_FAIL(SNNFLOW_E_ARG, "fwd_chain: pair of different shapes");
+        if (a.wt_rec || !b.wt_rec || !b.wt_rec_t)
+            SNN_FAIL(SNNFLOW_E_ARG, "fwd_chain: a pair is (feed-forward task, recurrent task)");
+        if (!pipe_task(a) || !pipe_task(b))
+            SNN_FAIL(SNNFLOW_E_ARG, "fwd_chain: pairs need the forward tile pipeline (SNNFLOW_PIPE_FWD > 0, no spike bit "
+                                    "planes, tensors under 2^31 bytes)");
+        // the hand-over replaces the second task's s_prev load: it names no buffer, and what the first task's
+        // LIF computes (its layer l-1: prev_y, prev_state, prev) is the second task's own layer one step
+        // earlier -- distinct from the second task's layer l-1 and from both outputs
+        if (b.s_prev) SNN_FAIL(SNNFLOW_E_ARG, "fwd_chain: the first task's spikes are handed to the second task (s_prev NULL)");
+        if (a.prev_state == b.prev_state || a.prev_y == b.prev_y || a.prev_y == b.y || a.y == b.y || a.y == b.prev_y ||
+            (a.prev_acc && a.prev_acc == b.prev_acc))
+            SNN_FAIL(SNNFLOW_E_ARG, "fwd_chain: the first task's layer l-1 is the second task's own layer one step earlier");
+        ++i;
+    }
+    return fwd_launch(conv, nconv, pair, lif, stream);
 }
 
 int snnflow_eval_slot(const snnflow_eval_fwd_args* tasks, int n, void* stream) {

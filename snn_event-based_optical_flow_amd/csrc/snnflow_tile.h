@@ -770,7 +770,7 @@ __device__ inline void pin(float (&v)[N]) {
 // function would be allocated once per instantiation, all of them in a wavefront launch).
 constexpr int kSumScratch = 8 * 4 * 48;  // waves x rows x sums (C = 32 backward: 3 * 16)
 __device__ inline float* sum_scratch() {
-    __shared__ float buf[kSumScratch];
+    __shared__ __attribute__((aligned(16))) float buf[kSumScratch];
     return buf;
 }
 

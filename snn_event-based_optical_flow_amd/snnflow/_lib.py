@@ -376,6 +376,8 @@ EXPORTS = {
     "snnflow_count_nonzero": (I32, [P, P, I32, P, P]),
     "snnflow_fwd_slot": (I32, [ctypes.POINTER(ConvFwdArgs), I32, ctypes.POINTER(LifFwdArgs), P]),
     "snnflow_bwd_slot": (I32, [ctypes.POINTER(LayerBwdArgs), I32, ctypes.POINTER(LifBwdArgs), P]),
+    "snnflow_fwd_chain": (I32, [ctypes.POINTER(ConvFwdArgs), I32, ctypes.POINTER(ctypes.c_ubyte),
+                                ctypes.POINTER(LifFwdArgs), P]),
     "snnflow_bwd_chain": (I32, [ctypes.POINTER(LayerBwdArgs), I32, ctypes.POINTER(ctypes.c_ubyte),
                                 ctypes.POINTER(LifBwdArgs), P]),
     "snnflow_slot_supported": (I32, [I32, I32]),
@@ -409,7 +411,7 @@ EXPORTS = {
     "snnflow_pointwise_bwd": (I32, [ctypes.POINTER(PointwiseArgs), P, I64, I64, P, P, P, P]),
 }
 MAX_SLOT_TASKS = 4
-MAX_CHAIN_TASKS = 7  # SNNFLOW_MAX_CHAIN_TASKS: layer tasks of one snnflow_bwd_chain launch
+MAX_CHAIN_TASKS = 7  # SNNFLOW_MAX_CHAIN_TASKS: layer tasks of one snnflow_bwd_chain / snnflow_fwd_chain launch
 MAX_COUNT_TENSORS = 16
 
 

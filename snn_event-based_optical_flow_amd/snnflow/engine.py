@@ -217,6 +217,12 @@ class FireNetEngine:
         # SNNFLOW_BWD_CHAIN=0 / 1 forces today's wavefront launches / the chained schedule.
         bc = os.environ.get("SNNFLOW_BWD_CHAIN")
         self.bwd_chain = True if bc is None else bc != "0"
+        # FireNetSequence forward at C = 8 with the tile pipeline: the launches of chained_fwd_slots (the
+        # task that computes a recurrent layer's spikes chained to that layer's next step in one block,
+        # snnflow_fwd_chain; T + L launches for LIFFireNet instead of 2(T-1) + L + 1).
+        # SNNFLOW_FWD_CHAIN=0 / 1 forces today's wavefront launches / the chained schedule.
+        fc = os.environ.get("SNNFLOW_FWD_CHAIN")
+        self.fwd_chain = True if fc is None else fc != "0"
         # forward_sequence: spike bit planes between its kernels (ABI 39; SNNFLOW_SPK_BITS=0: the fp32 spike
         # half of the states everywhere, as before)
         self.spk_bits = os.environ.get("SNNFLOW_SPK_BITS", "1") != "0"
@@ -1262,6 +1268,72 @@ def chained_bwd_slots(T, rec, chain=(), max_tasks=_lib.MAX_CHAIN_TASKS):
     return launches
 
 
+def chained_fwd_slots(T, rec, chain=(), max_tasks=_lib.MAX_CHAIN_TASKS):
+    """Launches of the forward of a T-step window over layers 0..L-1 (rec[l]: recurrent); task (k, t)
+    is the forward task of layer k at step t (the LIF of layer k-1 on the halo + the convs of layer k),
+    (L, t) the top task.  Task (k, t) follows
+      (k-1, t)    the pre-BN current of layer k-1 and its batch statistics,
+      (k, t-1)    the same layer's earlier step (membrane of layer k-1, running statistics; kept for the
+                  head too, so that the steps skew into an even wavefront),
+      (k+1, t-1)  where layer k is recurrent: its spikes of step t-1, computed by the next layer's task.
+    For r in `chain` the tasks (r+1, t-1) and (r, t) form one node, a chained pair run by one block per
+    tile (snnflow_fwd_chain): the third dependency stays inside the node, so the loop around layer r
+    costs one launch per step, not two.  Step 0's task of layer r and task (r+1, T-1) stay single.  A
+    node goes into the launch after its latest dependency (its longest-path level), or the next one
+    with room for its tasks (max_tasks conv tasks per launch).
+    Returns [[node, ...] per launch], node = ((k, t),) or ((r+1, t-1), (r, t)), layers ascending."""
+    L = len(rec)
+    chain = set(chain)
+    if not all(1 <= r < L - 1 and rec[r] and not rec[r + 1] for r in chain):
+        raise ValueError("chained_fwd_slots: a chained layer is recurrent, LIF-fed and followed by a feed-forward "
+                         "layer below the top")
+    node_of = {}
+    for k in range(L + 1):
+        for t in range(T):
+            if k in chain and t >= 1:
+                node = ((k + 1, t - 1), (k, t))
+            elif k - 1 in chain and t <= T - 2:
+                node = ((k, t), (k - 1, t + 1))
+            else:
+                node = ((k, t),)
+            node_of[(k, t)] = node
+
+    def deps(node):
+        out = set()
+        for k, t in node:
+            if k >= 1:
+                out.add((k - 1, t))
+            if t >= 1:
+                out.add((k, t - 1))
+                if k < L and rec[k]:
+                    out.add((k + 1, t - 1))
+        return {node_of[d] for d in out if d not in node}
+
+    level = {}
+
+    def lvl(node):  # longest path from a source (depth <= T + L nodes)
+        if node not in level:
+            level[node] = 1 + max((lvl(d) for d in deps(node)), default=-1)
+        return level[node]
+
+    nodes = sorted(set(node_of.values()), key=lambda n: (lvl(n), min(k for k, _ in n), n[0][1]))
+    slot, fill, launches = {}, [], []
+    for n in nodes:
+        s = 1 + max((slot[d] for d in deps(n)), default=-1)
+        nl = sum(1 for k, _ in n if k < L)
+        while s < len(fill) and fill[s] + nl > max_tasks:
+            s += 1
+        while len(launches) <= s:
+            launches.append([])
+            fill.append(0)
+        slot[n] = s
+        fill[s] += nl
+        launches[s].append(n)
+    for la in launches:
+        la.sort(key=lambda n: min(k for k, _ in n))
+    return launches
+
+
 def _state_rows(st_all, fin, T):
     """Flat per-step state rows of a FireNetSequence call: st_all's rows, the last one replaced by
     the caller's final_state_out buffer when there is one (st_all then has T - 1 rows)."""
@@ -1276,7 +1348,9 @@ class FireNetSequence(torch.autograd.Function):
     issued as wavefront launches (``wavefront_slots``, ``snnflow_fwd_slot`` /
     ``snnflow_bwd_slot``) that each run up to four independent layer-steps: a single
     layer-step of C = 8 at 128x128 occupies the chip for one latency-bound block round, so
-    the (L+1) x T launches of the per-step path are replaced by 2(T-1)+L+1.  The backward at C = 8
+    the (L+1) x T launches of the per-step path are replaced by 2(T-1)+L+1.  The forward at C = 8 runs
+    the chained schedule (``chained_fwd_slots``, ``snnflow_fwd_chain``): the task that computes a
+    recurrent layer's spikes and that layer's next step in one block, T + L launches.  The backward at C = 8
     runs the chained schedule instead (``chained_bwd_slots``, ``snnflow_bwd_chain``): the task of a
     recurrent layer and its consumer's in one block, T + L launches for LIFFireNet.  Batch-sum
     accumulators are per (step, layer) and zeroed once per call.  Inputs: eng, T, x_0..x_{T-1},
@@ -1371,12 +1445,27 @@ class FireNetSequence(torch.autograd.Function):
             # plane, or (fused weight gradients) when the layer is feed-forward: the next step's LIF reads
             # the membrane half and the backward recomputes the spikes
             return t < T - 1 and not eng.keep_seq_states and ((fuse and not eng.rec[l]) or need_bits[l])
-        for tasks in wavefront_slots(T, L + 1):
-            convs, top = [], None
-            for k, t in tasks:
+        # the chained schedule (C = 8, the forward tile pipeline, fp32 spike planes, tensors the pipeline's
+        # 32-bit offsets reach): the spikes of a chained layer at steps t-1 >= 0 pass from task (r+1, t-1) to
+        # task (r, t) inside a block; the spike half of its state is still written (the backward reads it)
+        chained = (bool(eng.fwd_chain) and C == 8 and L <= _lib.MAX_CHAIN_TASKS and not bits_on
+                   and lib.snnflow_get_pipe(0) > 0 and B * H * W * C * 4 < 2 ** 31)
+        if chained:
+            # tasks (k, t, second half of a chained pair): layer k, or k = L the top task
+            launches = [[(k, t, len(node) == 2 and i == 1) for node in la for i, (k, t) in enumerate(node)]
+                        for la in chained_fwd_slots(T, eng.rec, chainable_layers(eng.rec))]
+        else:
+            launches = [[(k, t, False) for k, t in tasks] for tasks in wavefront_slots(T, L + 1)]
+        for launch in launches:
+            convs, pairs, top = [], [], None
+            for k, t, second_half in launch:
                 if k < L:
                     a = _fwd_conv_args(eng, k, B, H, W, cin0, xs[t], ys[t], stats[t], states[t], mem_in[t],
                                        s_prev[t], facc[t], neurons, train, wfwd, wbwd)
+                    if second_half:  # its s_prev is handed over by the first half
+                        a.s_prev = None
+                        pairs[-1] = 1
+                    pairs.append(0)
                     if k >= 1 and spk_skip(k - 1, t):
                         a.state_spk_skip = 1
                     if k >= 1 and need_bits[k - 1]:
@@ -1390,8 +1479,13 @@ class FireNetSequence(torch.autograd.Function):
                     if spk_skip(L - 1, t):
                         top.state_spk_skip = 1
             arr = (_lib.ConvFwdArgs * max(len(convs), 1))(*convs)
-            _lib.call("fwd_slot", lib.snnflow_fwd_slot, arr, len(convs), ctypes.byref(top) if top is not None else None,
-                      s)
+            if chained:
+                _lib.call("fwd_slot", lib.snnflow_fwd_chain, arr, len(convs),
+                          (ctypes.c_ubyte * max(len(pairs), 1))(*pairs),
+                          ctypes.byref(top) if top is not None else None, s)
+            else:
+                _lib.call("fwd_slot", lib.snnflow_fwd_slot, arr, len(convs),
+                          ctypes.byref(top) if top is not None else None, s)
         _lib.timer_close()
 
         if eng.capture_states:  # tests / diagnostics: the window's pre-BN currents, statistics, batch sums

@@ -1,6 +1,6 @@
 """Per-task-kind attribution of the C = 8 wavefront slot launches from per-dispatch rocprofv3 data.
 
-    python tools/slot_attrib.py <counter_collection.csv | kernel_trace.csv> [fwd|bwd|bwdchain] [T] > out.json
+    python tools/slot_attrib.py <counter_collection.csv | kernel_trace.csv> [fwd|fwdchain|bwd|bwdchain] [T] > out.json
 
 Every slot launch of a LIFFireNet window holds a known mix of layer-steps (task (k, t) in launch
 k + 2t, engine.wavefront_slots), so a per-dispatch quantity -- a PMC counter, or the duration from a
@@ -17,6 +17,10 @@ bwdchain: the chained backward schedule (engine.chained_bwd_slots, T + L launche
   pair (the recurrent task (r, t+1) and the feed-forward task (r+1, t) in one block per tile).
 Forward (launch d: k + 2t = d): head (conv of the event counts), ff (LIF of layer k-1 + conv k),
 rec (the same + the recurrent conv), top (LIF of layer 6 + pred).
+fwdchain: the chained forward schedule (engine.chained_fwd_slots, T + L launches): head, ff, rec0 (the
+  recurrent layer's task of step 0, the only one left on its own), top, plus pair (the feed-forward task
+  (r+1, t-1) and the recurrent task (r, t) in one block per tile) -- set a pair's figure against ff + rec
+  of the plain fit for what the pair costs against the sum of its halves.
 """
 import collections
 import csv
@@ -29,16 +33,17 @@ from scipy.optimize import nnls
 L, REC = 7, (1, 4)
 
 
-def mix_chain(T):
+def mix_chain(T, forward=False):
     import os
     sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))),
                                     "snn_event-based_optical_flow_amd"))
-    from snnflow.engine import chained_bwd_slots
+    from snnflow.engine import chained_bwd_slots, chained_fwd_slots
 
-    kinds = ["top", "ff", "rec", "rec0", "head", "pair"]
+    # (forward: every recurrent task of a step t >= 1 is the second half of a pair, so "rec" stays empty)
+    kinds = ["head", "ff", "rec0", "top", "pair"] if forward else ["top", "ff", "rec", "rec0", "head", "pair"]
     rec = [l in REC for l in range(L)]
     rows = []
-    for launch in chained_bwd_slots(T, rec, REC):
+    for launch in (chained_fwd_slots if forward else chained_bwd_slots)(T, rec, REC):
         v = dict.fromkeys(kinds, 0)
         for node in launch:
             (k, t) = node[0]
@@ -49,7 +54,7 @@ def mix_chain(T):
             elif k == 0:
                 v["head"] += 1
             elif k in REC:
-                v["rec" if t >= 1 else "rec0"] += 1
+                v["rec" if (t >= 1 and not forward) else "rec0"] += 1
             else:
                 v["ff"] += 1
         rows.append([v[x] for x in kinds])
@@ -57,8 +62,8 @@ def mix_chain(T):
 
 
 def mix(direction, T):
-    if direction == "bwdchain":
-        return mix_chain(T)
+    if direction in ("bwdchain", "fwdchain"):
+        return mix_chain(T, direction == "fwdchain")
     K = L + 1
     kinds = ["top", "ff", "rec", "rec0", "head"] if direction == "bwd" else ["head", "ff", "rec", "top"]
     rows = []
@@ -114,7 +119,7 @@ def main():
     kinds, A1 = mix(direction, T)
     n = A1.shape[0]
     vals = {}
-    kdir = "bwd" if direction == "bwdchain" else direction
+    kdir = direction[:3]
     for kname in (f"k_{kdir}_slot<8>(", f"k_{kdir}_slot_t8(", f"k_{kdir}_slot_p8("):
         vals = dispatch_values(path, kname)  # (the C = 8 slot kernel the run launched)
         if vals:
