@@ -1150,6 +1150,55 @@ int snnflow_pointwise_fwd(const snnflow_pointwise_args* a, void* stream);
 int snnflow_pointwise_bwd(const snnflow_pointwise_args* a, const float* g_out, int64_t gs_b, int64_t gs_c,
                           float* g_w, float* g_b, double* scratch, void* stream);
 
+/* ---- membrane profiling (analyze_voltage_dynamics.py:33-241 VoltageProfiler,
+ *      eval_flow_quant.py:186-463 profile_membrane_ranges; csrc/profile.hip) ----
+ * Additive entries: the ABI version is unchanged.  One call folds n cell states, each
+ * [2][B][C][H][W] (membrane half, then spike half; all of one B, C, H, W and one storage order:
+ * SNNFLOW_LAYOUT_NHWC = the engine's [2][B][H][W][C], 16-byte aligned, or SNNFLOW_LAYOUT_NCHW =
+ * contiguous), into the persistent accumulators of the slots state i names (slot[i] in [0, nslots);
+ * a slot is a layer, several states of a call may share one).  Per slot, over every membrane value v
+ * (-0.0 counted as +0.0) and spike value s seen so far:
+ *   count            finite v                       nonfinite      NaN / +-inf v (excluded below)
+ *   chan_sum[C]      sum v (fp64)                   chan_sumsq[C]  sum v*v (product in fp64: exact)
+ *   chan_min[C]      exact minimum (+inf when empty)  chan_max[C]  exact maximum (-inf when empty)
+ *   chan_spikes[C]   number of s != 0
+ *   neuron_spikes    [H*W][C] number of s != 0 per neuron, summed over batch and calls
+ *   hist[65536]      (optional, NULL: off) counts of finite v by bin: with b the bits of v,
+ *                    key = (b >> 31) ? ~b : (b | 0x80000000), bin = key >> 16 (order-preserving; a bin
+ *                    is the floats of one bf16 truncation)
+ * Accumulators are caller-owned device memory, [nslots] x the shapes above, initialised by the caller
+ * (zeros, chan_min +inf, chan_max -inf).  Integer counts, extrema and the histogram are exact.  The
+ * fp64 sums take per-block partials through scratch, added in ascending block order after each
+ * thread added its slot's states in ascending call order: bit-reproducible for the same sequence of
+ * calls (no float atomics).  C in {4, 8, 16, 32, 64} (else SNNFLOW_E_CHANNELS); H*W <= 2^26, and a call
+ * that gives one block 2^32 values or more (its counts are 32-bit until the fold) is refused.  2 launches; no
+ * allocation, no host synchronisation.  scratch: snnflow_vstats_scratch_bytes(n, ...) bytes for a call
+ * with n distinct slots (the call's n is always enough; -1 for unsupported arguments), contents don't care. */
+#define SNNFLOW_VSTATS_MAX_TENSORS 96   /* a 10-step window of a 7-layer model (70 states) in one call */
+#define SNNFLOW_VSTATS_BINS 65536
+#define SNNFLOW_LAYOUT_NHWC 0
+#define SNNFLOW_LAYOUT_NCHW 1
+typedef struct snnflow_vstats_args {
+    int n, B, C, H, W, layout, nslots;
+    const float* state[SNNFLOW_VSTATS_MAX_TENSORS];
+    int slot[SNNFLOW_VSTATS_MAX_TENSORS];
+    uint64_t* count; uint64_t* nonfinite;        /* [nslots] */
+    double* chan_sum; double* chan_sumsq;        /* [nslots][C] */
+    float* chan_min; float* chan_max;            /* [nslots][C] */
+    uint64_t* chan_spikes;                       /* [nslots][C] */
+    uint32_t* neuron_spikes;                     /* [nslots][H*W][C] */
+    uint64_t* hist;                              /* [nslots][SNNFLOW_VSTATS_BINS] or NULL */
+    void* scratch; int64_t scratch_bytes;
+} snnflow_vstats_args;
+int snnflow_vstats_update(const snnflow_vstats_args* a, void* stream);
+int64_t snnflow_vstats_scratch_bytes(int n, int B, int C, int H, int W, int layout);
+/* Tuning, process-wide: how the histogram counts reach the table -- 0: integer atomics on the table in
+ * global memory; 1: through a per-block LDS sub-table of the 2048 bins of 2^-6 <= |v| < 4, flushed at the
+ * block's end (other bins as 0).  The table is the same either way.  Any other mode only queries.
+ * Returns the mode in force (default 1, the faster one measured; SNNFLOW_VSTATS_HIST_LDS=0 at load
+ * time selects 0). */
+int snnflow_vstats_hist_mode(int mode);
+
 const char* snnflow_last_error(void);
 int snnflow_abi_version(void);
 

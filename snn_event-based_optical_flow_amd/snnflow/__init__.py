@@ -13,6 +13,8 @@ from . import checkpoint, encodings  # noqa: F401  (checkpoint interchange, on-d
 from . import loader  # noqa: F401  (on-device batch preparation)
 from .loader import BatchPreparer
 from . import vis  # noqa: F401  (on-device frame renderers and percentiles)
+from . import profile  # noqa: F401  (on-device membrane profiling)
+from .profile import VoltageProfiler
 from .loss import EventWarping
 from .metrics import AAE, AAE_Filtered, AAE_Weighted, AE_ofMeans, AEE, NAAE, NEE
 from .optim import ClipAdam
@@ -24,4 +26,4 @@ __all__ = ["LIFFireNet", "LIFFireNet_short", "LIFFireFlowNet", "LIFFireFlowNet_s
            "SNNtorch_ConvLIFRecurrent", "ConvLIF", "ConvLIFRecurrent", "ConvLayer", "Leaky", "EventWarping", "AEE",
            "NEE", "AAE", "NAAE", "AE_ofMeans", "AAE_Weighted", "AAE_Filtered", "SpikingRecEVFlowNet",
            "SpikingMultiResUNetRecurrent", "SpikingRecurrentConvLayer", "SpikingResidualBlock", "SpikingUpsampleConvLayer",
-           "ClipAdam", "SnnflowError", "check_device_errors", "BatchPreparer"]
+           "ClipAdam", "SnnflowError", "check_device_errors", "BatchPreparer", "VoltageProfiler"]

@@ -177,6 +177,18 @@ class ErrorMapsArgs(ctypes.Structure):
                 ("dt_ratio", P), ("flow_scaling", F32), ("err", P), ("sum", P), ("count", P)]
 
 
+VSTATS_MAX_TENSORS = 96  # SNNFLOW_VSTATS_MAX_TENSORS
+VSTATS_BINS = 65536  # SNNFLOW_VSTATS_BINS
+LAYOUT_NHWC, LAYOUT_NCHW = 0, 1  # SNNFLOW_LAYOUT_*
+
+
+class VstatsArgs(ctypes.Structure):
+    _fields_ = [("n", I32), ("B", I32), ("C", I32), ("H", I32), ("W", I32), ("layout", I32), ("nslots", I32),
+                ("state", P * VSTATS_MAX_TENSORS), ("slot", I32 * VSTATS_MAX_TENSORS),
+                ("count", P), ("nonfinite", P), ("chan_sum", P), ("chan_sumsq", P), ("chan_min", P), ("chan_max", P),
+                ("chan_spikes", P), ("neuron_spikes", P), ("hist", P), ("scratch", P), ("scratch_bytes", I64)]
+
+
 ADAM_MAX_TENSORS = 64  # SNNFLOW_ADAM_MAX_TENSORS
 CLIP_ADAM_MAX_N = 1 << 20  # SNNFLOW_CLIP_ADAM_MAX_N
 
@@ -355,6 +367,9 @@ EXPORTS = {
     "snnflow_minmax_norm": (I32, [ctypes.POINTER(MinmaxNormArgs), P]),
     "snnflow_error_to_image": (I32, [P, I64, P, P]),
     "snnflow_error_maps": (I32, [ctypes.POINTER(ErrorMapsArgs), P]),
+    "snnflow_vstats_update": (I32, [ctypes.POINTER(VstatsArgs), P]),
+    "snnflow_vstats_scratch_bytes": (I64, [I32, I32, I32, I32, I32, I32]),
+    "snnflow_vstats_hist_mode": (I32, [I32]),
     "snnflow_convlif_bwd": (I32, [ctypes.POINTER(ConvLifBwdArgs), P]),
     "snnflow_convlif_param_grads": (I32, [P, P, P, I32, I32, P, P, P]),
     "snnflow_slab_reduce": (I32, [ctypes.POINTER(SlabDesc), I32, I32, P]),

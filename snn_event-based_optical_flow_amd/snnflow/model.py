@@ -7,7 +7,8 @@ Same class names, constructor (``unet_kwargs`` dict of ``configs/train_SNN.yml``
 A forward call is one fused time step on the GPU (engine.FireNetStep).  If forward
 hooks are registered on a cell, or the cells carry TEBN / MPBN normalisation
 (``unet_kwargs["tebn"|"mpbn"]``, ``models/model.py:74-83``), the cells are called one by one
-instead (hooks see the reference's ``(spk, state)`` outputs).
+instead (hooks see the reference's ``(spk, state)`` outputs).  An attached ``snnflow.VoltageProfiler``
+(``_profiler``) is handed every step's states instead of hooking the cells, so the fused path stays.
 """
 import copy
 import ctypes
@@ -78,6 +79,9 @@ class _FireNetBase(BaseModel):
     w_scale_pred = 0.01
     # (cell name, uses rec_neuron)
     layer_names = ()
+    # an attached snnflow.profile.VoltageProfiler (or None): handed every step's new states; unlike
+    # forward hooks it leaves the fused and wavefront launches in place
+    _profiler = None
 
     def __init__(self, unet_kwargs):
         super().__init__()
@@ -201,7 +205,8 @@ class _FireNetBase(BaseModel):
                 outs.append(self._step(x, log))
             return outs
         logging = isinstance(log, bool) and log and not self.exporting
-        eng.keep_seq_states = logging or eng.capture_states
+        prof = self._profiler
+        eng.keep_seq_states = logging or eng.capture_states or prof is not None
         try:
             if eval_fused_ok(eng, xs, self._states):  # eval mode, no autograd: conv + BN + LIF fused per task
                 flows, fin = eval_sequence(eng, xs, list(self._states))
@@ -212,6 +217,11 @@ class _FireNetBase(BaseModel):
             eng.keep_seq_states = False
         self._states = list(res[T:])
         outs = [{"flow": [f], "activity": None} for f in res[:T]]
+        if prof is not None:  # all T x L states of the window, SNNFLOW_VSTATS_MAX_TENSORS per launch
+            names = [n for n, _ in self.layer_spec]
+            prof.update_many(names * T, [st for sts in eng.seq_states for st in sts])
+            if not (logging or eng.capture_states):
+                eng.seq_states = None
         if logging:
             names = self._activity_names()
             sts, eng.seq_states = eng.seq_states, None
@@ -243,6 +253,8 @@ class _FireNetBase(BaseModel):
             flow, new_states = res[0], list(res[1:])
             self.__dict__["_states"] = new_states  # (plain attribute; skips Module.__setattr__)
             outs = None
+        if self._profiler is not None:
+            self._profiler.update_many([n for n, _ in self.layer_spec], self._states)
         activity = None
         if isinstance(log, bool) and log and not self.exporting:
             if outs is None:
