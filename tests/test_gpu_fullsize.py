@@ -20,6 +20,8 @@
 * get_interpolation / interpolate autograd against the oracle's torch restatement.
 """
 import copy
+import os
+import sys
 
 import numpy as np
 import pytest
@@ -35,139 +37,16 @@ pytestmark = pytest.mark.gpu
 GRAD_TOL = {"cfg2": 6e-6, "cfg3": 1.6e-5, "cfg2-C32": 5e-5, "cfg1": 1e-5}
 
 
-def _rel(a, b):
-    a, b = np.asarray(a, np.float64), np.asarray(b, np.float64)
-    return float(np.linalg.norm(a - b) / max(np.linalg.norm(b), 1e-30))
-
-
-def _cfg(H, W):
-    return {"loader": {"resolution": [H, W]}, "loss": {"flow_regul_weight": 0.001, "overwrite_intermediate": False},
-            "model": {"mask_output": True}}
-
-
-def _aee_pair(flow_ours, flow_ref, gt, mask, dev):
-    """AEE of our flow through snnflow.AEE (HIP) and of the oracle's flow through the oracle's
-    metric restatement (oracle/metrics_ref.py, pinned by eval_case.npz)."""
-    import snnflow
-    from oracle.metrics_ref import flow_metrics_ref
-
-    B, _, H, W = flow_ours.shape
-    m = snnflow.AEE(_cfg(H, W), dev, flow_scaling=128)
-    ev = torch.zeros(B, 1, 4, device=dev)
-    one = torch.ones(1)
-    m.event_flow_association([flow_ours], {"event_list": ev, "event_list_pol_mask": torch.zeros(B, 1, 2, device=dev),
-                                           "event_mask": mask.to(dev), "gtflow": gt.to(dev),
-                                           "dt_input": one, "dt_gt": one})
-    aee, _ = m()
-    ref = flow_metrics_ref(flow_ref, gt, mask, one, one, 128)["aee"]
-    return aee.cpu().numpy().astype(np.float64), ref.numpy().astype(np.float64)
-
-
-def _oracle_step(ref, x, ours, eps):
-    """One oracle time step, layer by layer (oracle/lif_ref.py LIFFireNetRef.forward).  Every
-    oracle spike that differs from ours (``ours``: our [2,B,C,H,W] states of this step) is
-    counted; if ``eps`` is set, a differing spike whose pre-reset membrane lies within eps of the
-    threshold (fp32-ill-conditioned) is replaced by ours, straight-through (value ours, the
-    oracle's graph and surrogate kept), with our reset membrane.  Returns (flow, flips per layer,
-    flips NOT within eps of the threshold)."""
-    h, flips, hard = x, [], 0
-    for i, (name, _) in enumerate(ref.spec):
-        cell = getattr(ref, name)
-        spk, st = cell(h, ref._states[i])
-        diff = spk.detach() != ours[i][1]
-        n = int(diff.sum())
-        flips.append(n)
-        if n:
-            near = (cell.lif.last_v - cell.lif.threshold.detach()).abs() <= (eps or 0.0)
-            hard += int((diff & ~near).sum())
-            if eps:
-                spk = spk + (ours[i][1] - spk).detach()
-                st = torch.stack([torch.where(diff, ours[i][0], st[0]), spk])
-        ref._states[i] = st
-        h = spk
-    return ref.pred(h), flips, hard
-
-
-def _new_model(C):
-    import snnflow
-    from oracle import lif_ref
-
-    torch.manual_seed(0)
-    return snnflow.LIFFireNet(lif_ref.make_unet_kwargs(base_num_channels=C))
-
-
-def _gpu_run(dev, path, wins, C):
-    """The train step's forward + loss + backward on the GPU; returns (model, initial state dict,
-    flows, loss, per-step CPU copies of the 7 states)."""
-    import snnflow
-
-    model = _new_model(C).to(dev).train()
-    init = {k: v.detach().cpu().clone() for k, v in model.state_dict().items()}
-    B, _, H, W = wins[0]["event_cnt"].shape
-    ew = snnflow.EventWarping(_cfg(H, W), dev)
-    states = []
-    if path == "sequence":
-        model.engine.capture_states = True
-        outs = model.forward_sequence([w["event_voxel"] for w in wins], [w["event_cnt"] for w in wins])
-        flows = [o["flow"][0] for o in outs]
-        states = [[s.detach().cpu() for s in sts] for sts in model.engine.seq_states]
-        model.engine.seq_states = None
-    else:
-        flows = []
-        for w in wins:
-            flows.append(model(w["event_voxel"], w["event_cnt"])["flow"][0])
-            states.append([s.detach().cpu() for s in model._states])
-    for t, w in enumerate(wins):
-        ew.event_flow_association([flows[t]], w["event_list"], w["event_list_pol_mask"], w["event_mask"])
-    loss = ew()
-    loss.backward()
-    return model, init, flows, loss.item(), states
-
-
-def _oracle_run(init, C, cpu_wins, ours_states, eps):
-    from oracle import iwe_ref, lif_ref
-
-    B, _, H, W = cpu_wins[0]["event_cnt"].shape
-    ref = lif_ref.LIFFireNetRef(lif_ref.make_unet_kwargs(base_num_channels=C), "LIFFireNet").train()
-    ref.load_state_dict(init)
-    rew = iwe_ref.EventWarpingRef([H, W], weight=0.001)
-    flows, flips, hard = [], [], 0
-    for t, w in enumerate(cpu_wins):
-        f, fl, hd = _oracle_step(ref, w["event_cnt"], ours_states[t], eps)
-        flows.append(f)
-        flips.append(fl)
-        hard += hd
-        rew.event_flow_association([f], w["event_list"], w["event_list_pol_mask"], w["event_mask"])
-    loss = rew()
-    loss.backward()
-    return ref, flows, loss.item(), np.array(flips), hard
-
-
-def _compare(tag, model, flows, loss, ref, rflows, rloss, flips, cpu_wins):
-    B, _, H, W = cpu_wins[0]["event_cnt"].shape
-    r = {"flips": flips, "loss": (loss, rloss),
-         "flow_rel": [_rel(f.detach().cpu().numpy(), q.detach().numpy()) for f, q in zip(flows, rflows)],
-         "flow_maxabs": max(float((f.detach().cpu() - q.detach()).abs().max()) for f, q in zip(flows, rflows)),
-         "grad_rel": {n: _rel(a.grad.cpu().numpy(), b.grad.numpy())
-                      for (n, a), (_, b) in zip(model.named_parameters(), ref.named_parameters())}}
-    gtg = torch.Generator().manual_seed(2)
-    gt = (torch.rand(B, 2, H, W, generator=gtg) - 0.5) * 8.0
-    r["aee"] = _aee_pair(flows[-1].detach(), rflows[-1].detach(), gt, cpu_wins[-1]["event_mask"],
-                         flows[-1].device)
-    _report(tag, r, B * model.engine.C * H * W)
-    return r
-
-
-def _report(tag, r, per_layer):
-    print(f"\n[{tag}] spike flips per step x layer (of {per_layer} each):\n{r['flips']}")
-    print(f"[{tag}] loss ours {r['loss'][0]:.9g} oracle {r['loss'][1]:.9g} "
-          f"rel {abs(r['loss'][0] - r['loss'][1]) / abs(r['loss'][1]):.3e}")
-    print(f"[{tag}] flow rel-L2 per step {['%.2e' % v for v in r['flow_rel']]} max|d| {r['flow_maxabs']:.3e}")
-    print(f"[{tag}] AEE ours {np.round(r['aee'][0], 6).tolist()} oracle {np.round(r['aee'][1], 6).tolist()} "
-          f"max|dAEE| {np.abs(r['aee'][0] - r['aee'][1]).max():.3e}")
-    worst = max(r["grad_rel"].items(), key=lambda kv: kv[1])
-    print(f"[{tag}] grad rel-L2 worst {worst[0]} {worst[1]:.3e}; all: "
-          + ", ".join(f"{k}={v:.1e}" for k, v in r["grad_rel"].items()))
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+# the train step against the oracle: shared with test_gpu_ragged.py / test_ragged_cpu.py
+from firenet_harness import aee_pair as _aee_pair  # noqa: E402
+from firenet_harness import cfg as _cfg  # noqa: E402
+from firenet_harness import compare as _compare  # noqa: E402
+from firenet_harness import gpu_run as _gpu_run  # noqa: E402
+from firenet_harness import new_model as _new_model  # noqa: E402
+from firenet_harness import oracle_run as _oracle_run  # noqa: E402
+from firenet_harness import oracle_step as _oracle_step  # noqa: E402
+from firenet_harness import rel as _rel  # noqa: E402
 
 
 # (tag, batch, resolution, base_num_channels, windows): BASELINE cfg2; cfg3 (256x256, B=4); the README /

@@ -156,6 +156,22 @@ def _spike_mismatch_ok(ours, ref, v, theta, tol=1e-4):
     return bool((bad & ~near).sum() == 0)
 
 
+def _adopt_near_threshold(tag, ours, ref, v, theta, tol=1e-4):
+    """The oracle's spikes with ours adopted (straight-through: value ours, the oracle's graph and
+    surrogate kept) where they differ and the oracle's pre-reset membrane v lies within tol of the
+    threshold.  A spike that differs anywhere else fails; the adoptions are counted and capped at 0.01 %
+    of the neurons (the share of a smooth membrane density that falls within 1e-4 of the threshold), so
+    that the gradient comparison that follows always runs.  Returns (spikes, mask of the adopted)."""
+    diff = ours != ref.detach()
+    near = (v - theta).abs() < tol
+    hard = int((diff & ~near).sum())
+    assert hard == 0, f"{tag}: {hard} spikes differ away from the threshold"
+    n = int(diff.sum())
+    print(f"\n[{tag}] adopted near-threshold spikes: {n} of {diff.numel()}")
+    assert n <= diff.numel() // 10000, (tag, n)
+    return ref + (ours - ref).detach(), diff
+
+
 @pytest.mark.parametrize("recurrent", [False, True])
 @pytest.mark.parametrize("C", [8, 16, 32])
 def test_cell_teacher_forced(dev, recurrent, C):
@@ -182,18 +198,19 @@ def test_cell_teacher_forced(dev, recurrent, C):
     v_ref = rst[0]
     np.testing.assert_allclose(cell.bn.running_mean.cpu().numpy(), ref.bn.running_mean.numpy(), rtol=1e-5, atol=1e-6)
     np.testing.assert_allclose(cell.bn.running_var.cpu().numpy(), ref.bn.running_var.numpy(), rtol=1e-5, atol=1e-6)
-    assert _spike_mismatch_ok(spk.detach().cpu(), rspk.detach(), v_ref.detach(), ref.lif.threshold.detach())
-    assert _rel(st[0].detach().cpu().numpy(), rst[0].detach().numpy()) < 1e-5
+    tag = f"cell C={C} rec={recurrent}"
+    rspk, adopted = _adopt_near_threshold(tag, spk.detach().cpu(), rspk, ref.lif.last_v, ref.lif.threshold.detach())
+    mem = torch.where(adopted, st[0].detach().cpu(), v_ref.detach())  # an adopted spike carries our reset membrane
+    assert _rel(st[0].detach().cpu().numpy(), mem.numpy()) < 1e-5
     wgt = torch.linspace(-1, 1, spk.numel()).view_as(spk)
     (spk * wgt.to(dev)).sum().backward()
     (rspk * wgt).sum().backward()
-    if (spk.detach().cpu() == rspk.detach()).all():
-        pairs = [(n, p.grad.cpu().numpy(), q.grad.numpy())
-                 for (n, p), (_, q) in zip(cell.named_parameters(), ref.named_parameters())]
-        pairs.append(("input", xd.grad.cpu().numpy(), xc.grad.numpy()))
-        if recurrent:
-            pairs.append(("prev_state", pd.grad.cpu().numpy(), pc.grad.numpy()))
-        _grad_check(f"cell C={C} rec={recurrent}", pairs, ORACLE_GRAD_TOL)
+    pairs = [(n, p.grad.cpu().numpy(), q.grad.numpy())
+             for (n, p), (_, q) in zip(cell.named_parameters(), ref.named_parameters())]
+    pairs.append(("input", xd.grad.cpu().numpy(), xc.grad.numpy()))
+    if recurrent:
+        pairs.append(("prev_state", pd.grad.cpu().numpy(), pc.grad.numpy()))
+    _grad_check(tag, pairs, ORACLE_GRAD_TOL)
 
 
 def _run_golden_firenet(g, name, dev, seq=False, norm=False, tol=GOLDEN_GRAD_TOL):
@@ -672,17 +689,20 @@ def test_convlif_vs_oracle_random(dev, recurrent, C, cin, hard):
             zc, sc = ref(xc, state_c, res)
         v = sc[0].detach()
         th = ref.thresh.detach().clamp_min(0.01)
-        assert _spike_mismatch_ok(sd[1].detach().cpu(), sc[1].detach(), v, th), t
+        # the cell's output is its spikes (+ the residual): ours adopted in it where the oracle's differ
+        # within 1e-4 of the threshold (the state's membrane half is the pre-reset membrane v itself)
+        zs, _ = _adopt_near_threshold(f"convlif C={C} cin={cin} rec={recurrent} hard={hard} step {t}",
+                                      sd[1].detach().cpu(), sc[1], v, th)
+        zc = zc + (zs - sc[1]).detach()
         np.testing.assert_allclose(sd[0].detach().cpu().numpy(), sc[0].detach().numpy(), rtol=1e-5, atol=1e-5)
         wz = torch.randn(B, C, H, W, generator=gen)
         wv = torch.randn(B, C, H, W, generator=gen)
         ((zd * wz.to(dev)).sum() + (sd[0] * wv.to(dev)).sum()).backward()
         ((zc * wz).sum() + (sc[0] * wv).sum()).backward()
-        if (sd[1].detach().cpu() == sc[1].detach()).all():
-            assert _rel(xd.grad.cpu().numpy(), xc.grad.numpy()) < 1e-4, t
-            assert _rel(state_d.grad.cpu().numpy(), state_c.grad.numpy()) < 1e-4, t
-            for (n, p), (_, q) in zip(cell.named_parameters(), ref.named_parameters()):
-                assert _rel(p.grad.cpu().numpy(), q.grad.numpy()) < 1e-4, (t, n)
+        assert _rel(xd.grad.cpu().numpy(), xc.grad.numpy()) < 1e-4, t
+        assert _rel(state_d.grad.cpu().numpy(), state_c.grad.numpy()) < 1e-4, t
+        for (n, p), (_, q) in zip(cell.named_parameters(), ref.named_parameters()):
+            assert _rel(p.grad.cpu().numpy(), q.grad.numpy()) < 1e-4, (t, n)
         cell.zero_grad()
         ref.zero_grad()
         # next step from OUR state (teacher forcing), fresh leaves
