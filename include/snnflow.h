@@ -1199,6 +1199,37 @@ int64_t snnflow_vstats_scratch_bytes(int n, int B, int C, int H, int W, int layo
  * time selects 0). */
 int snnflow_vstats_hist_mode(int mode);
 
+/* ---- contrast-maximisation landscape for global flows (tools/demo_iwe.py:46-102;
+ *      csrc/landscape.hip) ----
+ * Additive entries: the ABI version is unchanged.  The data term of EventWarping.forward
+ * (loss/flow.py:197-261: forward + backward warp, per sample) of ONE event window (max_ts = 1) for K
+ * candidate flows that every event of a sample shares: out[b][k] = fw_loss + bw_loss with
+ * (flow x, flow y) = cand[k] = (u, v) at every pixel.  The warp, the corner weights and the exact
+ * fixed-point accumulation are the loss kernels' own (snnflow_warp.h, snnflow_splat.h), so out[b][k]
+ * is what snnflow_iwe_loss_fwd computes for a constant flow map with weight 0, up to the order of the
+ * per-pixel sum; the call is bit-reproducible and a candidate's value does not depend on the other
+ * candidates of the call.  A sample whose forward or backward image is empty yields NaN (0/0, as the
+ * reference); an event whose two polarity masks are 0 contributes nothing.
+ * events [B][N][4] = (ts, y, x, p), ts in [0, 1], y / x integers inside the image, 16-byte aligned;
+ * pol [B][N][2]; cand [K][2]; out [B][K]; all float32, contiguous.  H*W <= 2^21, K >= 1, N >= 1,
+ * B*K <= 2^31 - 1 (one block per (sample, candidate)).  2 launches whatever K; no allocation, no
+ * host synchronisation.  scratch: snnflow_iwe_landscape_scratch_floats(...) floats, 16-byte aligned,
+ * contents don't care (the events binned by source row; it does not grow with K; -1 for unsupported
+ * arguments). */
+typedef struct snnflow_landscape_args {
+    int B, N, K, H, W;
+    int loss_scaling;
+    float flow_scaling;
+    const float* events;
+    const float* pol;
+    const float* cand;
+    float* out;
+    float* scratch;
+    int64_t scratch_floats;
+} snnflow_landscape_args;
+int snnflow_iwe_landscape(const snnflow_landscape_args* a, void* stream);
+int64_t snnflow_iwe_landscape_scratch_floats(int B, int N, int K, int H, int W);
+
 const char* snnflow_last_error(void);
 int snnflow_abi_version(void);
 

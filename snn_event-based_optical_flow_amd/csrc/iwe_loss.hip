@@ -13,6 +13,7 @@
 #include <cstdlib>
 
 #include "snnflow_dev.h"
+#include "snnflow_splat.h"
 #include "snnflow_warp.h"
 
 using namespace snnflow;
@@ -117,21 +118,9 @@ __device__ inline const float* mask_of(const snnflow_iwe_loss_args& a, int b, in
 // lists: every record is read once), re-warps them (the same warp4 on the same inputs: the same
 // corners and weights) and adds the corners inside the band, then writes the band once (no memset, no
 // global atomics).  images layout: [dir 2][img 4][B][HW].
-// Deterministic accumulation (SNNFLOW_SPLAT_FIXED, default): every corner contribution v is split
-// exactly into two 64-bit fixed-point integers, v = H 2^-32 + L 2^-75 (H = rint(v 2^32) in double,
-// L = rint((v - H 2^-32) 2^75): exact for |v| >= 2^-51), and the two are added with integer LDS
-// atomics.  Integer addition is associative, so the band totals -- the whole IWE -- are the same
-// bits on every run whatever order the records' atomics land in, and they are the exact sums of the
-// fp32 contributions (rounded once to fp32 at the end).  Two words because the loss reads ratios
-// (ts image / count image, loss/flow.py:219-233) that do not shrink with the weights: a pixel hit
-// only by a 1e-7 corner still contributes ts^2 to the loss, so the fraction needs relative, not
-// absolute, precision.  Range: |sum| < 2^31 per pixel and image.  (0: fp32 LDS atomics,
-// order-dependent rounding.)
-#ifndef SNNFLOW_SPLAT_FIXED
-#define SNNFLOW_SPLAT_FIXED 1
-#endif
-constexpr bool kSplatFixed = SNNFLOW_SPLAT_FIXED != 0;
-constexpr int SPLAT_NT = 1024, SB_BAND = 1024, WB_NT = 1024, WB_U = 2, kMaxSBands = 2048;  // H W <= 2^21 pixels
+// Deterministic accumulation: the band's images are SplatLds (snnflow_splat.h), exact two-word fixed point
+// by default, so the IWE does not depend on the order of the records' atomics.
+constexpr int WB_NT = 1024, WB_U = 2;
 // the loss backward's bins (k_iwe_bin / k_iwe_wbin, k_iwe_bwd_band): bands of GB_BAND pixels
 #ifndef SNNFLOW_GB_BAND
 #define SNNFLOW_GB_BAND 512
@@ -141,37 +130,9 @@ constexpr int SPLAT_NT = 1024, SB_BAND = 1024, WB_NT = 1024, WB_U = 2, kMaxSBand
 #endif
 constexpr int GB_NT = SNNFLOW_GB_NT, BIN_NT = 1024, GB_BAND = SNNFLOW_GB_BAND, kMaxBands = (1 << 21) / GB_BAND;  // H W <= 2^21 pixels
 
-struct SplatLdsF {  // fp32 images
-    float v[4][SB_BAND];
-    __device__ void zero(int tid) { for (int j = tid; j < 4 * SB_BAND; j += SPLAT_NT) (&v[0][0])[j] = 0.0f; }
-    __device__ void add(int q, int i, float x) { atomicAdd(&v[q][i], x); }
-    __device__ float get(int q, int i) const { return v[q][i]; }
-};
-struct SplatLdsX {  // exact two-word fixed point
-    unsigned long long hi[4][SB_BAND], lo[4][SB_BAND];
-    __device__ void zero(int tid) {
-        for (int j = tid; j < 4 * SB_BAND; j += SPLAT_NT) (&hi[0][0])[j] = 0, (&lo[0][0])[j] = 0;
-    }
-    __device__ void add(int q, int i, float x) {
-        // corner weights (x ts) lie in [0, 1]; the clamp keeps any input inside the fixed-point range
-        // (|d| < 2^30: rint(d 2^32) fits a 64-bit word with room for 2^31 additions)
-        const double d = fmin(fmax((double)x, -0x1p30), 0x1p30);
-        const double h = rint(d * 0x1p32);               // exact: x has 24 significant bits
-        const double r = d - h * 0x1p-32;                // exact, |r| <= 2^-33
-        const long long l = (long long)rint(r * 0x1p75);
-        atomicAdd(&hi[q][i], (unsigned long long)(long long)h);
-        if (l != 0) atomicAdd(&lo[q][i], (unsigned long long)l);  // zero for every |x| >= 2^-9
-    }
-    __device__ float get(int q, int i) const {
-        return (float)((double)(long long)hi[q][i] * 0x1p-32 + (double)(long long)lo[q][i] * 0x1p-75);
-    }
-};
-typedef std::conditional_t<kSplatFixed, SplatLdsX, SplatLdsF> SplatLds;
-
 // Records per (event, direction) at most: the non-zero corners of a warp lie within 2 W + 2 pixels
 // (y1 = floor(wy + 1) may exceed floor(wy) + 1 by one under rounding, likewise x1).
 __host__ __device__ inline int splat_rec_per_event(int W) { return (2 * W + 2) / SB_BAND + 2; }
-__host__ __device__ inline int splat_bands(int64_t HWp) { return (int)((HWp + SB_BAND - 1) / SB_BAND); }
 
 // The record scratch after the images: [B M R 2] records of 32 B ((b, k) region at R 2 (b M + off[k]))
 // and the bin table [B][T][2 nbands + 1] ints.

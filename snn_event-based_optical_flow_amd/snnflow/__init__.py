@@ -16,6 +16,8 @@ from . import vis  # noqa: F401  (on-device frame renderers and percentiles)
 from . import profile  # noqa: F401  (on-device membrane profiling)
 from .profile import VoltageProfiler
 from .loss import EventWarping
+from . import contrast  # noqa: F401  (on-device contrast-maximisation landscape for global flows)
+from .contrast import best_global_flow, flow_heatmap, loss_landscape
 from .metrics import AAE, AAE_Filtered, AAE_Weighted, AE_ofMeans, AEE, NAAE, NEE
 from .optim import ClipAdam
 from .model import LIFFireFlowNet, LIFFireFlowNet_short, LIFFireNet, LIFFireNet_short
@@ -26,4 +28,5 @@ __all__ = ["LIFFireNet", "LIFFireNet_short", "LIFFireFlowNet", "LIFFireFlowNet_s
            "SNNtorch_ConvLIFRecurrent", "ConvLIF", "ConvLIFRecurrent", "ConvLayer", "Leaky", "EventWarping", "AEE",
            "NEE", "AAE", "NAAE", "AE_ofMeans", "AAE_Weighted", "AAE_Filtered", "SpikingRecEVFlowNet",
            "SpikingMultiResUNetRecurrent", "SpikingRecurrentConvLayer", "SpikingResidualBlock", "SpikingUpsampleConvLayer",
-           "ClipAdam", "SnnflowError", "check_device_errors", "BatchPreparer", "VoltageProfiler"]
+           "ClipAdam", "SnnflowError", "check_device_errors", "BatchPreparer", "VoltageProfiler",
+           "loss_landscape", "flow_heatmap", "best_global_flow"]

@@ -245,6 +245,14 @@ class IweLossArgs(ctypes.Structure):
                 ("images", P), ("acc", P), ("persample", P), ("smooth", P), ("loss", P)]
 
 
+class LandscapeArgs(ctypes.Structure):
+    _fields_ = [("B", I32), ("N", I32), ("K", I32), ("H", I32), ("W", I32), ("loss_scaling", I32),
+                ("flow_scaling", F32), ("events", P), ("pol", P), ("cand", P), ("out", P), ("scratch", P),
+                ("scratch_floats", I64)]
+
+
+LANDSCAPE_MAX_PIXELS = 1 << 21  # H * W limit of snnflow_iwe_landscape (and of the loss)
+
 UNET_MAX_SEGS = 4
 UNET_MODE_S1, UNET_MODE_S2, UNET_MODE_T2 = 0, 1, 2
 UNET_EPI_STORE, UNET_EPI_LIF = 0, 1
@@ -378,6 +386,8 @@ EXPORTS = {
     "snnflow_device_errors": (I32, [I32]),
     "snnflow_iwe_scratch_floats": (I64, [I32, I32, I32, I32, I32, I32]),
     "snnflow_iwe_acc_doubles": (I32, [I32, I32, I32, I32]),
+    "snnflow_iwe_landscape": (I32, [ctypes.POINTER(LandscapeArgs), P]),
+    "snnflow_iwe_landscape_scratch_floats": (I64, [I32, I32, I32, I32, I32]),
     "snnflow_iwe_corners": (I32, [P, P, I32, I32, F32, I32, I32, F32, I32, P, P, P]),
     "snnflow_iwe_interpolate": (I32, [P, P, P, I64, I32, I32, I32, I32, P, P]),
     "snnflow_iwe_corners_bwd": (I32, [P, P, I32, I32, F32, I32, I32, F32, P, P, P]),
