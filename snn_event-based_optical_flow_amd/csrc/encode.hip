@@ -61,8 +61,9 @@ __global__ __launch_bounds__(NT) void k_encode(snnflow_encode_args a) {
 }  // namespace
 
 extern "C" int snnflow_encode_events(const snnflow_encode_args* a, void* stream) {
-    if (!a || a->B <= 0 || a->N < 0 || a->H <= 0 || a->W <= 0 || !a->ps || !a->ys || !a->xs ||
-        (a->voxel && (!a->ts || a->num_bins < 1)))
+    // an empty window (N == 0) has no event storage: its pointers may be NULL, the outputs are zeros
+    if (!a || a->B <= 0 || a->N < 0 || a->H <= 0 || a->W <= 0 ||
+        (a->N > 0 && (!a->ps || !a->ys || !a->xs || (a->voxel && !a->ts))) || (a->voxel && a->num_bins < 1))
         SNN_FAIL(SNNFLOW_E_ARG, "encode_events: bad args");
     const hipStream_t s = (hipStream_t)stream;
     const size_t HWp = (size_t)a->H * a->W;

@@ -351,8 +351,9 @@ extern "C" {
 
 int snnflow_pol_iwe(const float* events, const float* flow, const float* pol, int64_t pol_stride, int nimg, int B,
                     int N, int H, int W, float tref, float flow_scaling, int round_idx, float* out, void* stream) {
-    if (!events || !flow || !out || B <= 0 || N < 0 || H <= 0 || W <= 0 || nimg < 1 || nimg > 2 ||
-        (nimg == 2 && !pol))
+    // an empty window (N == 0) has no event or mask storage: its pointers may be NULL, the images are zeros
+    if (!flow || !out || B <= 0 || N < 0 || H <= 0 || W <= 0 || nimg < 1 || nimg > 2 ||
+        (N > 0 && (!events || (nimg == 2 && !pol))))
         SNN_FAIL(SNNFLOW_E_ARG, "pol_iwe: bad args");
     const hipStream_t s = (hipStream_t)stream;
     const int64_t HWp = (int64_t)H * W, nbands = (HWp + POLB_BAND - 1) / POLB_BAND;
