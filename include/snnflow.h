@@ -127,7 +127,7 @@ typedef struct snnflow_conv_fwd_args {
     double* acc;                /* += SNNFLOW_ACC_LEN(2c) (sum y, sum y^2); NULL = no batch sums (eval) */
     double* zero0; double* zero1; int zero_n;
     /* ABI 15, optional: bf16 fragments of wt_ff_t / wt_rec_t (snnflow_prep_desc.frag_fwd) for the
-     * spike convs of the cin == c kernels at c = 16, 32 (else split in the kernel) */
+     * spike convs of the cin == c kernels at c = 16, 32 (else split in the kernel; c = 8 ignores them) */
     const uint16_t* wf_ff; const uint16_t* wf_rec;
     /* ABI 33: 1 = store only the membrane half of prev_state (a caller whose spike half is never read:
      * a feed-forward layer's intermediate time steps in a window -- the backward recomputes the spikes) */
@@ -222,7 +222,10 @@ typedef struct snnflow_layer_bwd_args {
     double* acc_out;            /* += SNNFLOW_BWD_ACC(cin) sums for layer l-1 */
     double* zero0; double* zero1; int zero_n;
     /* ABI 15, optional: bf16 fragments of wt_fwd_ff / wt_fwd_rec (snnflow_prep_desc.frag_bwd)
-     * for the input-gradient convs of the cin == c kernels at c = 16, 32 (else f32 matrix cores) */
+     * for the input-gradient convs of the cin == c kernels.  c = 16, 32: read from global memory
+     * (else f32 matrix cores).  c = 8: copied into LDS by LDS-DMA, 16-byte aligned, wd_rec
+     * set wherever the recurrent input gradient is computed; NULL: split in every block from the
+     * fp32 weights (the same bits) */
     const uint16_t* wd_ff; const uint16_t* wd_rec;
     /* ABI 23, optional: the layer's weight gradients fused into this backward task (lif_in = 1,
      * c = cin = 8, wavefront launches only -- snnflow_bwd_slot; the single-task call ignores them).
@@ -982,7 +985,7 @@ typedef struct snnflow_firenet_plan {
     const float* wt_bwd_rec[SNNFLOW_MAX_LAYERS];
     const uint16_t* wf_ff[SNNFLOW_MAX_LAYERS];   /* forward fragments (c = 16, 32) or NULL */
     const uint16_t* wf_rec[SNNFLOW_MAX_LAYERS];
-    const uint16_t* wd_ff[SNNFLOW_MAX_LAYERS];   /* input-gradient fragments or NULL */
+    const uint16_t* wd_ff[SNNFLOW_MAX_LAYERS];   /* input-gradient fragments (c = 8, 16, 32) or NULL */
     const uint16_t* wd_rec[SNNFLOW_MAX_LAYERS];
     double* fwd_acc; int64_t fwd_acc_stride;     /* [L][stride] doubles, zero_n = stride */
     double* bwd_acc; int64_t bwd_acc_stride;

@@ -1539,6 +1539,38 @@ struct WAcc {
     }
 };
 
+typedef __attribute__((address_space(3))) void lds_void;
+
+template <int N>
+__device__ inline void vm_wait() {  // s_waitcnt vmcnt(N), the other counters untouched
+    static_assert(N >= 0 && N < 64, "vmcnt");
+    __builtin_amdgcn_s_waitcnt((N & 15) | ((N >> 4) << 14) | (7 << 4) | (15 << 8));
+}
+
+// FragStage<8, 8>'s LDS image (the B operand of a C = 8 input-gradient conv) from the prepared
+// fragments in global memory (snnflow_prep_desc.frag_bwd, split once per step by k_prep_weights; the
+// same layout) by LDS-DMA: 9 wave-loads of 64 x 16 B, dealt to the block's NW waves; no register holds
+// a weight.  w1 set: the packed operand of FragStage::load2, columns n >= 8 (lanes with bit 3 set) from
+// columns n - 8 of the second conv's image, as a second transfer under the complementary lane mask (an
+// LDS-DMA lane's destination follows its position in the wave, also when other lanes are masked).
+// The caller waits (vm_wait) before the barrier that precedes the first read.
+constexpr int kFragStage8Bytes = FragStage<8, 8, 64>::HALFS * 2;
+template <int NW>
+__device__ inline void frag_stage8_dma(const uint16_t* w0, const uint16_t* w1, float* dst) {
+    const int lane = threadIdx.x & 63;
+    const int wv = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);
+    const __amdgpu_buffer_rsrc_t rs0 = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint16_t*>(w0), (short)0, kFragStage8Bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs1 =
+        __builtin_amdgcn_make_buffer_rsrc(const_cast<uint16_t*>(w1 ? w1 : w0), (short)0, kFragStage8Bytes, 0x00020000);
+    const bool second = w1 != nullptr && (lane & 8) != 0;
+    const int src = (second ? lane - 8 : lane) * 16;
+    for (int k = wv; k < kFragStage8Bytes / 1024; k += NW) {
+        lds_void* d = (lds_void*)(reinterpret_cast<char*>(dst) + k * 1024);
+        if (!second) __builtin_amdgcn_raw_ptr_buffer_load_lds(rs0, d, 16, (uint32_t)(k * 1024 + src), 0, 0, 0);
+        else __builtin_amdgcn_raw_ptr_buffer_load_lds(rs1, d, 16, (uint32_t)(k * 1024 + src), 0, 0, 0);
+    }
+}
+
 // chain (wavefront launches, C = 8 with the fused weight gradients): the two halves of a chained pair
 // run in one block, the recurrent task (l, t+1) with chain = 1 and then the feed-forward task (l+1, t)
 // with chain = 2 on the same tile.  The first half computes the recurrent input gradient as if
@@ -1585,6 +1617,23 @@ __device__ void layer_bwd_body(const snnflow_layer_bwd_args& a, const Grid g, fl
     [[maybe_unused]] constexpr bool TR = LIF_IN && CIN == C && SNNFLOW_TRACE_LAYER;
     [[maybe_unused]] constexpr int TK = REC ? 3 : 2;
     TRACE_AT(TR, TK, 0);
+
+    // 0. C = 8 with the prepared fragments passed (wd_ff / wd_rec): their image goes straight to the
+    //    fragment regions by LDS-DMA, ahead of every other load (an LDS access may wait for it: then it
+    //    waits for nothing issued later).  A chained pair's second half runs this after the barrier
+    //    between the halves, and is feed-forward: only wl_x, free by then, is written; the hand-over
+    //    in wl_r stays.  Without the pointers the block splits the fp32 weights itself (step 1).
+    [[maybe_unused]] bool fdma = false;
+    if constexpr (LB::BF6 && C == 8 && CIN == 8) {
+        fdma = a.wt_bwd_ff != nullptr && a.wd_ff != nullptr && (!has_gsp || a.wd_rec != nullptr);
+        if (fdma) {
+            if constexpr (REC) {
+                frag_stage8_dma<NTB / 64>(a.wd_ff, has_gsp ? a.wd_rec : nullptr, wl_x);  // packed: ff | rec columns
+            } else {
+                frag_stage8_dma<NTB / 64>(a.wd_ff, nullptr, wl_x);
+            }
+        }
+    }
 
     // 1. every global load of the kernel, issued up front (register prefetch; weights for LDS);
     //    the BN-sum replicas first, so that their reduction overlaps the halo loads
@@ -1640,7 +1689,9 @@ __device__ void layer_bwd_body(const snnflow_layer_bwd_args& a, const Grid g, fl
     constexpr bool PKC = FLDS && REC && CIN == 8 && C == 8;
     [[maybe_unused]] const bool pkr = PKC && a.wt_bwd_ff != nullptr && has_gsp;
     if constexpr (FLDS) {
-        if constexpr (PKC) {
+        if (fdma) {
+            // (the prepared image is on its way: step 0)
+        } else if constexpr (PKC) {
             if (pkr) fs_x.load2(a.wt_fwd_ff, a.wt_fwd_rec);
             else if (a.wt_bwd_ff) fs_x.load(a.wt_fwd_ff);
             if (!pkr && has_gsp) fs_r.load(a.wt_fwd_rec);
@@ -1804,9 +1855,13 @@ __device__ void layer_bwd_body(const snnflow_layer_bwd_args& a, const Grid g, fl
         }
     }
     if constexpr (FLDS) {
-        if (a.wt_bwd_ff) fs_x.store(reinterpret_cast<__bf16*>(wl_x));
-        if constexpr (REC) {
-            if (has_gsp && !pkr) fs_r.store(reinterpret_cast<__bf16*>(wl_r));
+        if (fdma) {
+            vm_wait<0>();  // this wave's part of the fragment image has landed (the barrier: every wave's)
+        } else {
+            if (a.wt_bwd_ff) fs_x.store(reinterpret_cast<__bf16*>(wl_x));
+            if constexpr (REC) {
+                if (has_gsp && !pkr) fs_r.store(reinterpret_cast<__bf16*>(wl_r));
+            }
         }
     }
     __syncthreads();
@@ -3498,14 +3553,6 @@ __device__ inline int slot_task(const __attribute__((address_space(4))) P* pp, G
 // tile.  Same arithmetic as conv_fwd_body<8, 8, true, REC, 2> (the conv in another summation
 // order inside the matrix core only where the hardware's k-order differs).
 // ---------------------------------------------------------------------------
-typedef __attribute__((address_space(3))) void lds_void;
-
-template <int N>
-__device__ inline void vm_wait() {  // s_waitcnt vmcnt(N), the other counters untouched
-    static_assert(N >= 0 && N < 64, "vmcnt");
-    __builtin_amdgcn_s_waitcnt((N & 15) | ((N >> 4) << 14) | (7 << 4) | (15 << 8));
-}
-
 // A value the compiler cannot treat as loop-invariant (forces per-iteration recomputation of what
 // derives from it instead of holding it in registers across the loop).
 __device__ inline int opaque_int(int v) {

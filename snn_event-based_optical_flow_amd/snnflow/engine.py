@@ -115,7 +115,7 @@ class PreppedWeights:
         self.fwd = {}
         self.bwd = {}
         self.frag = {}   # i -> uint16 [snnflow_frag_halfs] forward-conv bf16 fragments (C = 16, 32) or None
-        self.fragb = {}  # i -> the same for the input-gradient conv
+        self.fragb = {}  # i -> the same for the input-gradient conv (C = 8, 16, 32)
         self.key = None
         self.gen = 0  # bumped whenever the buffers are re-allocated
 
@@ -150,8 +150,9 @@ class PreppedWeights:
                 self.fwd[i] = torch.empty(w.numel(), device=w.device)
                 self.bwd[i] = torch.empty(w.numel(), device=w.device)
                 c, cin = w.shape[0], w.shape[1]
-                nf = lib.snnflow_frag_halfs(c, cin) if c >= 16 else 0  # C = 8 splits in LDS
-                self.frag[i] = torch.empty(nf, dtype=torch.int16, device=w.device) if nf else None
+                nf = lib.snnflow_frag_halfs(c, cin)  # 0 for the head (cin != c)
+                # (C = 8: only the backward kernels take an image, FireNetEngine.frag8)
+                self.frag[i] = torch.empty(nf, dtype=torch.int16, device=w.device) if nf and c >= 16 else None
                 self.fragb[i] = torch.empty(nf, dtype=torch.int16, device=w.device) if nf else None
                 fresh = True
         self.shapes = shapes
@@ -223,6 +224,12 @@ class FireNetEngine:
         # SNNFLOW_FWD_CHAIN=0 / 1 forces today's wavefront launches / the chained schedule.
         fc = os.environ.get("SNNFLOW_FWD_CHAIN")
         self.fwd_chain = True if fc is None else fc != "0"
+        # C = 8 backward: the C x C convs' bf16 hi / mid / lo input-gradient fragments, split once per step
+        # by the weight preparation, are passed to the backward kernels (wd_ff / wd_rec), which copy the
+        # image into LDS instead of splitting the fp32 weights in every block (the same bits either way).
+        # SNNFLOW_FRAG8=0 / engine.frag8 = False: the pointers stay NULL at C = 8.  The forward kernels
+        # always split in the block at C = 8 (their share measured no gain: DESIGN 4.1), wf_* stay NULL.
+        self.frag8 = os.environ.get("SNNFLOW_FRAG8", "1") != "0"
         # forward_sequence: spike bit planes between its kernels (ABI 39; SNNFLOW_SPK_BITS=0: the fp32 spike
         # half of the states everywhere, as before)
         self.spk_bits = os.environ.get("SNNFLOW_SPK_BITS", "1") != "0"
@@ -333,6 +340,19 @@ class FireNetEngine:
             ps += [cell.bn.weight, cell.bn.bias, cell.lif.beta, cell.lif.threshold]
         ps += [self.pred.weight, self.pred.bias]
         return ps
+
+    def frag_fwd(self, l):
+        """(ff, rec) prepared fragments of layer l's forward convs as the kernels take them, or Nones
+        (C = 8 has none: the forward kernels split in the block)."""
+        fr = self.__dict__.get("frags")
+        return (None, None) if fr is None else fr[l]
+
+    def frag_bwd(self, l):
+        """The same for layer l's input-gradient convs (C = 8: engine.frag8)."""
+        fb = self.__dict__.get("fragsb")
+        if fb is None or (self.C == 8 and not self.frag8):
+            return None, None
+        return fb[l]
 
     def workspace(self, B, H, W, device):
         key = (B, H, W, self.C, device)
@@ -514,7 +534,7 @@ class FireNetEngine:
         neurons = self.neurons()
         train = tuple(bn.training or not bn.track_running_stats for bn in self.bns)
         key = (B, H, W, cin0, id(ws), ws.fwd_acc.data_ptr(), self.prep.gen, self._gen, train,
-               self.pred.weight.data_ptr(), self.pred.bias.data_ptr())
+               self.pred.weight.data_ptr(), self.pred.bias.data_ptr(), self.frag8)
         pl = self.__dict__.get("_plan")
         if pl is not None and pl[0] == key:
             return pl[1]
@@ -529,8 +549,8 @@ class FireNetEngine:
             p.n[l] = neurons[l]
             p.wt_fwd_ff[l], p.wt_fwd_rec[l] = _ptr_t(wfwd[l][0]), _ptr_t(wfwd[l][1])
             p.wt_bwd_ff[l], p.wt_bwd_rec[l] = _ptr_t(wbwd[l][0]), _ptr_t(wbwd[l][1])
-            p.wf_ff[l], p.wf_rec[l] = _ptr_t(self.frags[l][0]), _ptr_t(self.frags[l][1])
-            p.wd_ff[l], p.wd_rec[l] = _ptr_t(self.fragsb[l][0]), _ptr_t(self.fragsb[l][1])
+            p.wf_ff[l], p.wf_rec[l] = (_ptr_t(f) for f in self.frag_fwd(l))
+            p.wd_ff[l], p.wd_rec[l] = (_ptr_t(f) for f in self.frag_bwd(l))
             p.slab_ff[l], p.slab_rec[l] = _ptr_t(ws.slab_ff[l]), _ptr_t(ws.slab_rec[l])
         p.fwd_acc, p.fwd_acc_stride = ws.fwd_acc.data_ptr(), ws.fwd_acc.stride(0)
         p.bwd_acc, p.bwd_acc_stride = ws.bwd_acc.data_ptr(), ws.bwd_acc.stride(0)
@@ -630,9 +650,8 @@ def _fwd_conv_args(eng, l, B, H, W, cin0, x, ys, stats, states, mem_in, s_prev, 
     a.wt_ff_t, a.wt_rec_t = ptr(wbwd[l][0]), ptr(wbwd[l][1])  # MFMA B operand layout
     a.s_prev = _ptr_t(s_prev[l])
     a.y, a.acc = ys[l], (facc[l] if train[l] else None)
-    fr = getattr(eng, "frags", None)
-    if fr is not None:  # pre-split bf16 fragments of the spike convs (C = 16, 32)
-        a.wf_ff, a.wf_rec = _ptr_t(fr[l][0]), _ptr_t(fr[l][1])
+    # pre-split bf16 fragments of the spike convs (C = 16, 32)
+    a.wf_ff, a.wf_rec = (_ptr_t(f) for f in eng.frag_fwd(l))
     return a
 
 
@@ -682,9 +701,8 @@ def _bwd_layer_args(eng, l, B, H, W, cin0, ys, stats, mem_in, neurons, gst, gcur
         if g_prev[l] is not None:
             a.g_state_prev = ptr(g_prev[l])
             a.zero_mem_half = 0 if ext[l] else 1
-    fb = getattr(eng, "fragsb", None)
-    if fb is not None:  # pre-split bf16 fragments of the input-gradient convs (C = 16, 32)
-        a.wd_ff, a.wd_rec = _ptr_t(fb[l][0]), _ptr_t(fb[l][1])
+    # pre-split bf16 fragments of the input-gradient convs (C = 16, 32; C = 8: engine.frag8)
+    a.wd_ff, a.wd_rec = (_ptr_t(f) for f in eng.frag_bwd(l))
     if l > 0:
         a.cin, a.lif_in = C, 1
         a.wt_bwd_ff, a.wt_fwd_ff = ptr(wbwd[l][0]), ptr(wfwd[l][0])
