@@ -6,16 +6,9 @@
 #include <cmath>
 
 #include "snnflow_dev.h"
+#include "snnflow_host.h"
 
 using namespace snnflow;
-
-int snnflow_set_error(int code, const char* msg);
-#define SNN_FAIL(code, msg) return snnflow_set_error((code), (msg))
-#define SNN_CHECK_LAUNCH()                                                        \
-    do {                                                                          \
-        hipError_t e_ = hipGetLastError();                                        \
-        if (e_ != hipSuccess) return snnflow_set_error((int)e_, hipGetErrorString(e_)); \
-    } while (0)
 
 namespace {
 

@@ -8,9 +8,7 @@
 #include <cstring>
 
 #include "snnflow_dev.h"
-
-int snnflow_set_error(int code, const char* msg);
-#define SNN_FAIL(code, msg) return snnflow_set_error((code), (msg))
+#include "snnflow_host.h"
 
 namespace {
 

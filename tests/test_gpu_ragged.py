@@ -1,7 +1,7 @@
-"""The LIFFireNet kernels (csrc/lif_layers.hip, csrc/snnflow_tile.h: Conv3x3 + BatchNorm + LIF on
-8 x 32-pixel tiles with a one-pixel halo) at image sizes that are no tile multiples, against the CPU
-oracle in fp64 (tests/firenet_harness.py).  Every test has the oracle on the other side; none compares
-two GPU paths.
+"""The LIFFireNet kernels (csrc/lif_layers.hip, csrc/wgrad.hip, csrc/snnflow_tile.h: Conv3x3 + BatchNorm
++ LIF on 8 x 32-pixel tiles with a one-pixel halo) at image sizes that are no tile multiples, against
+the CPU oracle in fp64 (tests/firenet_harness.py).  Every test has the oracle on the other side; none
+compares two GPU paths.
 
 a. one cell, one step, teacher-forced (test_cell_ragged): C in {4, 8, 16, 32}, feed-forward and
    recurrent, train and eval mode -- spikes, membrane, running statistics, every gradient.

@@ -1,11 +1,12 @@
 #!/bin/bash
 # Register / LDS / spill usage of the kernels of one translation unit (gfx950), from the compiler's
 # resource-usage remarks:  tools/kres.sh lif_layers.hip [kernel-name-regex]
+# (the unit's own flags come from the Makefile: make unit_flags S=<stem>)
 set -u
 F=${1:-lif_layers.hip}; PAT=${2:-.}
 cd snn_event-based_optical_flow_amd/csrc
 /opt/rocm/bin/hipcc -O3 -std=c++17 --offload-arch=gfx950 -fPIC -ffp-contract=off -I../../include -I. \
-  $( [ "$F" = lif_layers.hip ] && echo -mllvm -amdgpu-inline-max-bb=2000 ) --cuda-device-only -c $F -o /tmp/kres.o -Rpass-analysis=kernel-resource-usage 2>&1 |
+  $(make -s unit_flags S=${F%.hip}) --cuda-device-only -c $F -o /tmp/kres.o -Rpass-analysis=kernel-resource-usage 2>&1 |
   python3 -c "
 import re,sys
 pat=re.compile(sys.argv[1]); cur=None; rows=[]
