@@ -473,6 +473,68 @@ int snnflow_loader_prepare(const snnflow_loader_args* a, void* stream);
 int64_t snnflow_loader_scratch_floats(int B, int N, int H0, int W0, int Ht, int Wt, int num_bins, int hot_enabled,
                                       int keep_gt_full_res);
 
+/* ---- on-device sequence reading (ABI 41, additive) ----
+ * The file side of the reference's H5Loader (dataloader/h5.py:47-70 state, 138-175 window
+ * bounds, 184-283 restart rules, 350-365 ground truth and row advance, 449-545 centre-crop
+ * search; dataloader/encodings.py:9-27 index search) over recordings that live in device
+ * memory: one call cuts the next window of every batch slot and writes exactly what
+ * snnflow_loader_prepare reads.
+ *
+ * Slot b keeps row[b] (event index / time / fractional flow index, float64 as in the
+ * reference's Python floats), batch_idx[b] (running sequence counter; the slot reads sequence
+ * batch_idx[b] % nseq) and status[b] (SNNFLOW_SEQ_* bits, sticky until the caller clears them).
+ * Modes: EVENTS (window = event count; with Hc < H0 or Wc < W0 the first `window` events inside
+ * the centred Hc x Wc crop, searched in chunks of 2*window, doubling up to 5*window while less
+ * than half is collected, for at most 10*window searched events; coordinates shifted by the crop
+ * origin), TIME (window = seconds; [row + t0, row + t0 + window) by the reference's bisection)
+ * and GTFLOW (window = flow maps, fractional below 1).  A slot whose window cannot be cut
+ * restarts: row = 0, batch_idx[b] = max(batch_idx) + 1, in slot order, as often as needed within
+ * the call (restarts[b] counts them); after nseq restarts without a usable sequence the slot
+ * gets SNNFLOW_SEQ_STUCK and an empty window.  A window of at most 10 events is delivered empty.
+ * A window of more than N events delivers its first N and sets SNNFLOW_SEQ_OVERFLOW.
+ * ts = float32(ts - t0) with the subtraction in float64; dt_input = (ts_last - t0) - (ts_first - t0)
+ * in float64 (0 for an empty window); dt_gt = flow_ts[i] - flow_ts[i - 1] of the delivered map i
+ * (0 when i == 0 or outside GTFLOW).  Rows of xs/ys/ts/ps behind counts[b] are zeros.  Integer,
+ * float64 and single-rounding arithmetic in a fixed order: every output is reproducible bit for
+ * bit.  2 launches, no float atomics, no host synchronisation. */
+#define SNNFLOW_SEQ_EVENTS 0
+#define SNNFLOW_SEQ_TIME 1
+#define SNNFLOW_SEQ_GTFLOW 2
+#define SNNFLOW_SEQ_OVERFLOW 1
+#define SNNFLOW_SEQ_STUCK 2
+typedef struct snnflow_seq_desc {
+    const int16_t* xs; const int16_t* ys;   /* [n] pixel coordinates inside H0 x W0 */
+    const double* ts;                       /* [n] absolute timestamps, non-decreasing */
+    const uint8_t* ps;                      /* [n] polarity in {0, 1} */
+    int64_t n;
+    double t0;                              /* attrs["t0"] */
+    double last_ts;                         /* ts[n - 1] (t0 when n == 0) */
+    int64_t nflow;                          /* F ground-truth maps (GTFLOW) */
+    const double* flow_ts;                  /* [F] */
+    const float* flow_maps;                 /* [F][2][H0][W0] */
+} snnflow_seq_desc;
+typedef struct snnflow_seq_args {
+    int B, N;
+    int mode;                   /* SNNFLOW_SEQ_EVENTS / _TIME / _GTFLOW */
+    int nseq;
+    int H0, W0;                 /* frame of the recordings (loader.std_resolution) */
+    int Hc, Wc;                 /* EVENTS: crop (loader.resolution), <= frame; else == frame */
+    double window;              /* data.window; EVENTS: a whole number <= N */
+    const snnflow_seq_desc* seqs;   /* [nseq], device memory */
+    double* row;                /* [B] state */
+    int64_t* batch_idx;         /* [B] state */
+    int* status;                /* [B] state, bits are only ever set */
+    int64_t* scratch;           /* SNNFLOW_SEQ_SCRATCH_WORDS(B, N) words; word 0 zero before the first call */
+    int64_t scratch_words;
+    float* xs; float* ys; float* ts; float* ps;     /* [B][N] */
+    int* counts;                /* [B] */
+    double* dt_input; double* dt_gt;                /* [B] */
+    float* gtflow;              /* [B][2][H0][W0], GTFLOW only (NULL otherwise) */
+    int* restarts;              /* [B] sequence changes of the slot in this call */
+} snnflow_seq_args;
+#define SNNFLOW_SEQ_SCRATCH_WORDS(B, N) (2 + 3 * (int64_t)(B) + (int64_t)(B) * (N))
+int snnflow_seq_next(const snnflow_seq_args* a, void* stream);
+
 /* Sums per-block weight-gradient slabs: out[i][e] = sum_b slab[i][b][e]. */
 typedef struct snnflow_slab_desc { const float* slab; float* out; int elems; } snnflow_slab_desc;
 #define SNNFLOW_MAX_SLABS 16

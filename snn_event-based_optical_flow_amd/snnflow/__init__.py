@@ -12,6 +12,8 @@ from .convlif import ConvLIF, ConvLIFRecurrent
 from . import checkpoint, encodings  # noqa: F401  (checkpoint interchange, on-device event encodings)
 from . import loader  # noqa: F401  (on-device batch preparation)
 from .loader import BatchPreparer
+from . import sequence  # noqa: F401  (on-device sequence reading: resident recordings -> raw windows)
+from .sequence import EventSequence, SequenceLoader, SequenceReader
 from . import vis  # noqa: F401  (on-device frame renderers and percentiles)
 from . import profile  # noqa: F401  (on-device membrane profiling)
 from .profile import VoltageProfiler
@@ -29,4 +31,5 @@ __all__ = ["LIFFireNet", "LIFFireNet_short", "LIFFireFlowNet", "LIFFireFlowNet_s
            "NEE", "AAE", "NAAE", "AE_ofMeans", "AAE_Weighted", "AAE_Filtered", "SpikingRecEVFlowNet",
            "SpikingMultiResUNetRecurrent", "SpikingRecurrentConvLayer", "SpikingResidualBlock", "SpikingUpsampleConvLayer",
            "ClipAdam", "SnnflowError", "check_device_errors", "BatchPreparer", "VoltageProfiler",
+           "EventSequence", "SequenceReader", "SequenceLoader",
            "loss_landscape", "flow_heatmap", "best_global_flow"]

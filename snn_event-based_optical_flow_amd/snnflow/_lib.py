@@ -139,6 +139,27 @@ class LoaderArgs(ctypes.Structure):
                 ("gtflow", P), ("scratch", P)]
 
 
+SEQ_EVENTS, SEQ_TIME, SEQ_GTFLOW = 0, 1, 2  # SNNFLOW_SEQ_* modes
+SEQ_OVERFLOW, SEQ_STUCK = 1, 2  # SNNFLOW_SEQ_* status bits
+
+
+class SeqDesc(ctypes.Structure):
+    _fields_ = [("xs", P), ("ys", P), ("ts", P), ("ps", P), ("n", I64), ("t0", F64), ("last_ts", F64),
+                ("nflow", I64), ("flow_ts", P), ("flow_maps", P)]
+
+
+class SeqArgs(ctypes.Structure):
+    _fields_ = [("B", I32), ("N", I32), ("mode", I32), ("nseq", I32), ("H0", I32), ("W0", I32), ("Hc", I32),
+                ("Wc", I32), ("window", F64), ("seqs", P), ("row", P), ("batch_idx", P), ("status", P),
+                ("scratch", P), ("scratch_words", I64), ("xs", P), ("ys", P), ("ts", P), ("ps", P), ("counts", P),
+                ("dt_input", P), ("dt_gt", P), ("gtflow", P), ("restarts", P)]
+
+
+def seq_scratch_words(B, N):
+    """SNNFLOW_SEQ_SCRATCH_WORDS"""
+    return 2 + 3 * B + B * N
+
+
 class AeeArgs(ctypes.Structure):
     _fields_ = [("B", I32), ("H", I32), ("W", I32), ("flow", P), ("gtflow", P), ("event_mask", P),
                 ("dt_ratio", P), ("flow_scaling", F32), ("acc", P), ("aee", P), ("percent", P),
@@ -364,6 +385,7 @@ EXPORTS = {
     "snnflow_encode_events": (I32, [ctypes.POINTER(EncodeArgs), P]),
     "snnflow_loader_prepare": (I32, [ctypes.POINTER(LoaderArgs), P]),
     "snnflow_loader_scratch_floats": (I64, [I32, I32, I32, I32, I32, I32, I32, I32, I32]),
+    "snnflow_seq_next": (I32, [ctypes.POINTER(SeqArgs), P]),
     "snnflow_pol_iwe":(I32, [P, P, P, I64, I32, I32, I32, I32, I32, F32, F32, I32, P, P]),
     "snnflow_aee": (I32, [ctypes.POINTER(AeeArgs), P]),
     "snnflow_aee_acc_doubles": (I32, [I32, I32, I32]),
