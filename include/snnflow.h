@@ -341,6 +341,41 @@ typedef struct snnflow_wgrad_args {
 } snnflow_wgrad_args;
 int snnflow_wgrad(const snnflow_wgrad_args* a, void* stream);
 
+/* ---- K x K cells: model.kernel_size 1, 5, 7 (additive; the ABI version is unchanged) ----
+ * The reference's cells take any kernel size (configs/train_SNN.yml:20 `kernel_size`, passed on by
+ * models/model.py:68, 249, 424, 594; SNNtorch_spiking_submodules.py pads by kernel_size // 2).  The
+ * calls above are written for 3 x 3 and a one-pixel halo; these are their lif_in = 0 halves for an
+ * odd k in {1, 5, 7} at stride 1 (csrc/convk.hip), which is what a cell-wise step of a model with
+ * kernel_size != 3 runs around the kernel-size-agnostic snnflow_lif_fwd / snnflow_lif_bwd /
+ * snnflow_slab_reduce.  They reuse the argument structs of the 3 x 3 calls with every `3` read as k:
+ * weights [k][k][cin][c] / [k][k][c][cin], slab rows of c * cin * k * k floats; the tile, the block
+ * count (snnflow_conv_blocks) and the accumulator layouts are the same.  Inputs are arbitrary fp32
+ * values (nothing is assumed to be a spike) and the arithmetic is exact f32: v_mfma_f32_16x16x4_f32
+ * for the c x c convs at c >= 8 and all weight gradients, vector FMAs for cin in {1, 2, 4, 5} and c = 4.
+ * Fields that only the 3 x 3 fast paths read must be NULL / 0 (SNNFLOW_E_ARG otherwise): wf_*, wd_*,
+ * spike bit planes, wslab_*, prev_*, state_spk_skip (and layer_bwd's s_prev, x, has_pred).
+ * k outside {1, 5, 7} is SNNFLOW_E_ARG (3 belongs to the calls above); a channel pair outside
+ * c in {4, 8, 16, 32}, cin in {1, 2, 4, 5, c} is SNNFLOW_E_CHANNELS. */
+/* 1 if the four calls below take (k, c, cin) for a feed-forward (rec = 0) / recurrent (rec = 1) cell, else 0 */
+int snnflow_convk_supported(int k, int c, int cin, int rec);
+/* snnflow_prep_weights for a [c][cin][k][k] weight: wt_fwd [k][k][cin][c], wt_bwd [k][k][c][cin]
+ * (either may be NULL).  The conv weights of `ff` / `rec` (SNNtorch_spiking_submodules.py:222-229, :443-450). */
+int snnflow_prep_weights_k(const float* w, int c, int cin, int k, float* wt_fwd, float* wt_bwd, void* stream);
+/* snnflow_conv_fwd with lif_in = 0: y = ff(x) [+ rec(s_prev)], pre-BN NHWC, and the batch sums of its
+ * `bn` into acc (real pixels only) -- SNNtorch_spiking_submodules.py:289-292 and :521-540.  The c x c
+ * convs at c >= 8 read wt_ff_t / wt_rec_t, the others wt_ff / wt_rec. */
+int snnflow_convk_fwd(const snnflow_conv_fwd_args* a, int k, void* stream);
+/* snnflow_layer_bwd with lif_in = 0: block 0 turns acc_in into the neuron / BatchNorm parameter
+ * gradients and writes bnc_out; every block forms G = BN-backward(g_cur, y, stats) on its tile plus
+ * halo and writes g_x (strided, when g_x and wt_bwd_ff are set) and, for recurrent cells, the spike
+ * half of g_state_prev (honouring zero_mem_half): the transposed k x k convs, i.e. autograd's backward
+ * of the lines above.  The c x c convs at c >= 8 read wt_fwd_ff / wt_fwd_rec, the others wt_bwd_*. */
+int snnflow_layerk_bwd(const snnflow_layer_bwd_args* a, int k, void* stream);
+/* snnflow_wgrad for k x k: per-tile slab rows [snnflow_conv_blocks()][c * cin * k * k] (+ [..][c * c * k * k]),
+ * accumulated over nsteps in a fixed order, then written or added; bit-identical run to run.
+ * exact_inputs is not read. */
+int snnflow_wgradk(const snnflow_wgrad_args* a, int k, void* stream);
+
 /* ---- U-Net neuron flavour: ConvLIF / ConvLIFRecurrent ----------------------
  * models/spiking_submodules.py:121-151 (ConvLIF, stride 1), :265-300 (ConvLIFRecurrent):
  *   I = conv_ff(x) [+ conv_rec(z_prev)];  leak = sigmoid(leak_raw);  th = clamp_min(thresh, 0.01)

@@ -381,6 +381,11 @@ EXPORTS = {
     "snnflow_lif_bwd": (I32, [ctypes.POINTER(LifBwdArgs), P]),
     "snnflow_layer_bwd": (I32, [ctypes.POINTER(LayerBwdArgs), P]),
     "snnflow_wgrad": (I32, [ctypes.POINTER(WgradArgs), P]),
+    "snnflow_convk_supported": (I32, [I32, I32, I32, I32]),
+    "snnflow_prep_weights_k": (I32, [P, I32, I32, I32, P, P, P]),
+    "snnflow_convk_fwd": (I32, [ctypes.POINTER(ConvFwdArgs), I32, P]),
+    "snnflow_layerk_bwd": (I32, [ctypes.POINTER(LayerBwdArgs), I32, P]),
+    "snnflow_wgradk": (I32, [ctypes.POINTER(WgradArgs), I32, P]),
     "snnflow_convlif_fwd": (I32, [ctypes.POINTER(ConvLifFwdArgs), P]),
     "snnflow_encode_events": (I32, [ctypes.POINTER(EncodeArgs), P]),
     "snnflow_loader_prepare": (I32, [ctypes.POINTER(LoaderArgs), P]),

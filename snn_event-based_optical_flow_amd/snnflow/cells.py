@@ -77,9 +77,16 @@ class Leaky(nn.Module):
         return self.mem
 
 
+# model.kernel_size values with kernels: 3 on the fused / wavefront paths (csrc/lif_layers.hip), 1, 5 and 7 on
+# the cell-wise path (csrc/convk.hip)
+KERNEL_SIZES = (1, 3, 5, 7)
+
+
 def _check_supported(kernel_size, stride, quantization_config, tebn, mpbn, norm, detach, activation):
-    if kernel_size != 3 or stride != 1:
-        raise NotImplementedError("snnflow cells implement the reference's 3x3 / stride-1 convolutions")
+    if stride != 1:
+        raise NotImplementedError("snnflow cells implement the reference's stride-1 convolutions")
+    if kernel_size not in KERNEL_SIZES:
+        raise NotImplementedError(f"snnflow cells implement kernel_size in {KERNEL_SIZES} (got {kernel_size!r})")
     if quantization_config is not None and quantization_config.get("enabled", False):
         raise NotImplementedError("quantized (brevitas) cells are out of scope (DESIGN.md)")
     if norm not in (None, "weight"):
@@ -94,6 +101,7 @@ class _SnnTorchCellBase(nn.Module):
     def _build(self, input_size, hidden_size, kernel_size, leak, thresh, learn_leak, learn_thresh, hard_reset,
                stride=1, tebn=False, num_timesteps=4, mpbn=False, detach=True):
         self.input_size, self.hidden_size = input_size, hidden_size
+        self.kernel_size = kernel_size
         pad = kernel_size // 2
         beta_init = torch.empty(hidden_size, 1, 1).uniform_(leak[0], leak[1])
         threshold_init = torch.empty(hidden_size, 1, 1).uniform_(thresh[0], thresh[1])
@@ -258,10 +266,13 @@ class _CellPrep:
 
 
 def _prep(w, s):
-    c, cin = w.shape[0], w.shape[1]
-    fwd = torch.empty(9 * cin * c, device=w.device)
-    bwd = torch.empty(9 * cin * c, device=w.device)
-    _lib.call("prep_weights", lib.snnflow_prep_weights, ptr(w.detach().contiguous()), c, cin, ptr(fwd), ptr(bwd), None, s)
+    c, cin, k = w.shape[0], w.shape[1], w.shape[2]
+    fwd = torch.empty(k * k * cin * c, device=w.device)
+    bwd = torch.empty(k * k * cin * c, device=w.device)
+    if k == 3:
+        _lib.call("prep_weights", lib.snnflow_prep_weights, ptr(w.detach().contiguous()), c, cin, ptr(fwd), ptr(bwd), None, s)
+    else:
+        _lib.call("prep_weights_k", lib.snnflow_prep_weights_k, ptr(w.detach().contiguous()), c, cin, k, ptr(fwd), ptr(bwd), s)
     return fwd, bwd
 
 
@@ -271,8 +282,11 @@ class CellFn(torch.autograd.Function):
         _lib.require_device(x, "cell input")
         B, cin, H, W = x.shape
         C = cell.hidden_size
+        K = cell.kernel_size
         dev = x.device
         s = _lib.stream_ptr(dev)
+        if K != 3 and not lib.snnflow_convk_supported(K, C, cin, 1 if cell.recurrent else 0):
+            raise NotImplementedError(f"no {K}x{K} cell kernel for {cin} -> {C} channels")
         _lib.call("threshold clamp", lib.snnflow_prep_weights, None, C, 1, None, None, ptr(cell.lif.threshold), s)
         wff = _prep(params[0], s)  # the conv weights as passed (weight norm: the effective g v / ||v||)
         wrec = _prep(params[1], s) if cell.recurrent else (None, None)
@@ -297,7 +311,10 @@ class CellFn(torch.autograd.Function):
         a.wt_ff, a.wt_rec, a.s_prev = ptr(wff[0]), _ptr_t(wrec[0]), _ptr_t(sp)
         a.wt_ff_t, a.wt_rec_t = ptr(wff[1]), _ptr_t(wrec[1])
         a.y, a.acc = ptr(y), (ptr(facc) if n.bn_train else None)
-        _lib.call("conv_fwd", lib.snnflow_conv_fwd, ctypes.byref(a), s)
+        if K == 3:
+            _lib.call("conv_fwd", lib.snnflow_conv_fwd, ctypes.byref(a), s)
+        else:
+            _lib.call("convk_fwd", lib.snnflow_convk_fwd, ctypes.byref(a), K, s)
         state = empty_state(B, C, H, W, dev)
         f = _lib.LifFwdArgs()
         f.B, f.H, f.W, f.c = B, H, W, C
@@ -324,6 +341,7 @@ class CellFn(torch.autograd.Function):
         sp = rest.pop(0) if ctx.has_sp else None
         B, cin, H, W = x.shape
         C = cell.hidden_size
+        K = cell.kernel_size
         dev = x.device
         s = _lib.stream_ptr(dev)
         ws = _cell_ws(B, H, W, C, dev)
@@ -353,8 +371,6 @@ class CellFn(torch.autograd.Function):
         b.g_cur, b.acc = ptr(g_cur), ptr(bacc)
         _lib.call("lif_bwd", lib.snnflow_lif_bwd, ctypes.byref(b), s)
 
-        slab_ff = torch.empty(ws.nblk, C * cin * 9, device=dev)
-        slab_rec = torch.empty(ws.nblk, C * C * 9, device=dev) if cell.recurrent else None
         bnc = torch.empty(2, C, device=dev)
         a = _lib.LayerBwdArgs()
         a.B, a.H, a.W, a.cin, a.c, a.lif_in = B, H, W, cin, C, 0
@@ -369,11 +385,14 @@ class CellFn(torch.autograd.Function):
             a.wt_bwd_rec, a.wt_fwd_rec = ptr(ctx.wbwd[1]), ptr(ctx.wfwd[1])
             if g_prev is not None:
                 a.g_state_prev, a.zero_mem_half = ptr(g_prev), 0
-        _lib.call("layer_bwd", lib.snnflow_layer_bwd, ctypes.byref(a), s)
+        if K == 3:
+            _lib.call("layer_bwd", lib.snnflow_layer_bwd, ctypes.byref(a), s)
+        else:
+            _lib.call("layerk_bwd", lib.snnflow_layerk_bwd, ctypes.byref(a), K, s)
         theta_subtract(cell, g_cur, mem, B * H * W, ptr(g_th), s)
         # weight gradients of this single step (snnflow_wgrad with one step)
-        slab_ff = torch.empty(ws.nblk, C * cin * 9, device=dev)
-        slab_rec = torch.empty(ws.nblk, C * C * 9, device=dev) if cell.recurrent else None
+        slab_ff = torch.empty(ws.nblk, C * cin * K * K, device=dev)
+        slab_rec = torch.empty(ws.nblk, C * C * K * K, device=dev) if cell.recurrent else None
         wa = _lib.WgradArgs()
         wa.B, wa.H, wa.W, wa.cin, wa.c, wa.nsteps, wa.accumulate = B, H, W, cin, C, 1, 0
         wa.rec = 1 if cell.recurrent else 0
@@ -383,12 +402,15 @@ class CellFn(torch.autograd.Function):
         st.x = ptr(x)
         st.xs_b, st.xs_c, st.xs_h, st.xs_w = _x_strides(x)
         st.s_prev = _ptr_t(sp) if cell.recurrent else None
-        _lib.call("wgrad", lib.snnflow_wgrad, ctypes.byref(wa), s)
-        g_wff = torch.empty(cell.hidden_size, cin, 3, 3, device=dev)
+        if K == 3:
+            _lib.call("wgrad", lib.snnflow_wgrad, ctypes.byref(wa), s)
+        else:
+            _lib.call("wgradk", lib.snnflow_wgradk, ctypes.byref(wa), K, s)
+        g_wff = torch.empty(cell.hidden_size, cin, K, K, device=dev)
         descs = [_lib.SlabDesc(ptr(slab_ff), ptr(g_wff), g_wff.numel())]
         g_wrec = None
         if cell.recurrent:
-            g_wrec = torch.empty(C, C, 3, 3, device=dev)
+            g_wrec = torch.empty(C, C, K, K, device=dev)
             descs.append(_lib.SlabDesc(ptr(slab_rec), ptr(g_wrec), g_wrec.numel()))
         arr = (_lib.SlabDesc * len(descs))(*descs)
         _lib.call("slab_reduce", lib.snnflow_slab_reduce, arr, len(descs), ws.nblk, s)

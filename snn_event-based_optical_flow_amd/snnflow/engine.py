@@ -198,6 +198,7 @@ class FireNetEngine:
         self.pred = model.pred.conv2d
         self.L = len(self.cells)
         self.C = self.cells[0].hidden_size
+        self.kernel_size = getattr(self.cells[0], "kernel_size", 3)
         self.ws = None
         self.prep = PreppedWeights()
         self.bwd_open = False
@@ -306,8 +307,8 @@ class FireNetEngine:
         return any(lif.reset_mechanism == "subtract" for lif in self.lifs)
 
     def sequence_ok(self, cin0):
-        """True if FireNetSequence's wavefront launches take this model (C = 8, 16, 32; cin0 2 or 4)."""
-        return bool(lib.snnflow_slot_supported(self.C, cin0))
+        """True if FireNetSequence's wavefront launches take this model (3x3 convs; C = 8, 16, 32; cin0 2 or 4)."""
+        return self.kernel_size == 3 and bool(lib.snnflow_slot_supported(self.C, cin0))
 
     # parameter order = Function input order after the states
     def param_list(self):
@@ -1699,10 +1700,12 @@ def eval_fused_ok(eng, xs, prev=()):
     BatchNorm on running statistics, no autograd needed -- neither the parameters nor any input or
     initial state require grad while grad mode is on (saliency / adversarial evaluation keeps the
     autograd path) --, 2- or 4-bin input on the GPU, and not disabled by SNNFLOW_EVAL_FUSED=0 (the
-    train-path split launches then run in eval mode too)."""
+    train-path split launches then run in eval mode too).  3x3 models only."""
     import os
     x = xs[0]
     if os.environ.get("SNNFLOW_EVAL_FUSED", "1") == "0" or eng.C != 8 or not x.is_cuda or x.shape[1] not in (2, 4):
+        return False
+    if eng.kernel_size != 3:  # the fused evaluation tasks are 3x3 kernels
         return False
     if any(bn.training or not bn.track_running_stats for bn in eng.bns):
         return False

@@ -96,6 +96,7 @@ class _FireNetBase(BaseModel):
                 kw.update(unet_kwargs["spiking_neuron"])
         C = unet_kwargs["base_num_channels"]
         k = unet_kwargs["kernel_size"]
+        self.kernel_size = k
         q = unet_kwargs.get("quantization", {})
         tebn = unet_kwargs.get("tebn", {})
         tebn = tebn.get("enabled", False) if isinstance(tebn, dict) else bool(tebn)
@@ -162,9 +163,11 @@ class _FireNetBase(BaseModel):
 
     def _cellwise(self):
         """Cells called one by one (each an autograd node on the HIP cell kernels): forward hooks
-        registered, TEBN / MPBN cells (their extra normalisation sits between the fused kernels), or
-        weight-normalised convolutions (the effective weights are formed per call)."""
-        return self._hooked() or any(c.tebn_enabled or c.mpbn_enabled or getattr(c, "weight_norm", False)
+        registered, TEBN / MPBN cells (their extra normalisation sits between the fused kernels),
+        weight-normalised convolutions (the effective weights are formed per call), or a kernel size
+        other than 3 (the fused step, the wavefront / chained launches and the fused evaluation are
+        3x3 kernels; 1, 5 and 7 have cell kernels only, csrc/convk.hip)."""
+        return self.kernel_size != 3 or self._hooked() or any(c.tebn_enabled or c.mpbn_enabled or getattr(c, "weight_norm", False)
                                      for c in self._mods()[:-1])
 
     def _input(self, event_voxel, event_cnt):
@@ -190,7 +193,9 @@ class _FireNetBase(BaseModel):
         run instead (engine.eval_sequence: conv + BatchNorm + LIF per task, T + L - 1 launches).  With
         ``log`` the T activity dicts come from one count launch per 16 tensors and one read-back.
         Falls back to T ``forward`` calls where those launches do not apply (hooks, TEBN/MPBN,
-        C = 4)."""
+        C = 4, ``kernel_size`` 1, 5 or 7: the fused per-step plan, the wavefront and chained launches
+        and the fused evaluation are 3x3-only, so such a model runs cell by cell with exactly the
+        results of T ``forward`` calls)."""
         seq = event_voxels if self.encoding == "voxel" else event_cnts
         T = len(seq)
         none = [None] * T
