@@ -1278,6 +1278,38 @@ __device__ inline void vm_wait() {  // s_waitcnt vmcnt(N), the other counters un
     __builtin_amdgcn_s_waitcnt((N & 15) | ((N >> 4) << 14) | (7 << 4) | (15 << 8));
 }
 
+// s_waitcnt lgkmcnt(0): every LDS read this wave has issued has returned.  Ahead of an LDS-DMA into the
+// bytes just read (the DMA is ordered behind nothing but the issuing wave's own counters); no memory
+// access moves across it.
+__device__ inline void lds_reads_done() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }
+
+// A block barrier over LDS accesses alone: s_waitcnt lgkmcnt(0); s_barrier.  __syncthreads() carries a
+// release fence, for which the compiler also waits for the wave's LDS-DMA in flight (vmcnt(0)); the
+// forward tile pipeline keeps its next halo in flight across both barriers of a phase, and no wave reads
+// another's DMA (or global stores) in its loop.
+__device__ inline void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
+
+// A thread's four LIF coefficient records (channels 4 qt .. 4 qt + 3) from LDS, read and waited for in
+// one asm block.  As C++ loads they carry no alias-scope metadata (coef is no part of the pool), and in
+// front of such an LDS access the compiler's wait-count pass waits for every LDS-DMA in flight
+// (vmcnt(0)): behind the refill of the tile pipeline that is the wait the refill was moved up to cover.
+// (The pool's own accesses carry the metadata and get no such wait: check the loop for vmcnt after a change.)
+__device__ inline void load_coef4(const LifCoef* coef, int qt, LifCoef (&kc)[4]) {
+    static_assert(sizeof(LifCoef) == 16, "one 16-B load per record");
+    const uint32_t addr = (uint32_t)(uintptr_t)(const lds_void*)(coef + 4 * qt);
+    f32x4 v0, v1, v2, v3;
+    asm volatile(
+        "ds_read_b128 %0, %4\n\tds_read_b128 %1, %4 offset:16\n\tds_read_b128 %2, %4 offset:32\n\t"
+        "ds_read_b128 %3, %4 offset:48\n\ts_waitcnt lgkmcnt(0)"
+        : "=&v"(v0), "=&v"(v1), "=&v"(v2), "=&v"(v3)
+        : "v"(addr)
+        : "memory");
+    kc[0] = LifCoef{v0[0], v0[1], v0[2], v0[3]};
+    kc[1] = LifCoef{v1[0], v1[1], v1[2], v1[3]};
+    kc[2] = LifCoef{v2[0], v2[1], v2[2], v2[3]};
+    kc[3] = LifCoef{v3[0], v3[1], v3[2], v3[3]};
+}
+
 // FragStage<8, 8>'s LDS image (the B operand of a C = 8 input-gradient conv) from the prepared
 // fragments in global memory (snnflow_prep_desc.frag_bwd, split once per step by k_prep_weights; the
 // same layout) by LDS-DMA: 9 wave-loads of 64 x 16 B, dealt to the block's NW waves; no register holds
@@ -2050,9 +2082,11 @@ __device__ inline int slot_task(const __attribute__((address_space(4))) P* pp, G
 //     v_permlane32_swap per register packs the wave's two 16-pixel M-tiles into 64 lanes -- the
 //     pre-BN current leaves as one 16-B store per lane (no LDS staging, no barrier) and the
 //     batch sums stay in registers over the block's tiles (one set of fp64 atomics per block).
-// Per tile: wait(DMA) + barrier -> LIF of layer l-1 over the halo from LDS (state stores,
-// spikes as a bf16 tile) -> barrier -> DMA of the next tile -> MFMA -> store.  Two barriers per
-// tile.  Same arithmetic as conv_fwd_body<8, 8, true, REC, 2> (the conv in another summation
+// Per tile: wait(DMA) -> the wave's raw halo elements from LDS into registers -> DMA of the next tile
+// into the same chunks (a wave issues exactly the chunks it reads: no barrier in between) -> barrier
+// -> LIF of layer l-1 (state stores, spikes as a bf16 tile) -> barrier -> MFMA -> store.  Two barriers
+// per tile (lds_barrier: the DMA stays in flight across them), the DMA under the LIF phase and the
+// conv.  Same arithmetic as conv_fwd_body<8, 8, true, REC, 2> (the conv in another summation
 // order inside the matrix core only where the hardware's k-order differs).
 // ---------------------------------------------------------------------------
 // A value the compiler cannot treat as loop-invariant (forces per-iteration recomputation of what
@@ -2110,7 +2144,7 @@ __device__ void fwd_lif8_pipe(const snnflow_conv_fwd_args& a, const Grid g, floa
     constexpr int C = 8, NTB = 2 * NT, R = Halo4<C, NTB>::R;
     using L = PipeFwdLds<REC>;
     char* const lds = reinterpret_cast<char*>(pool);
-    __shared__ LifCoef coef[C];
+    __shared__ __attribute__((aligned(16))) LifCoef coef[C];  // (load_coef4: 16-B reads)
     __shared__ double sums[2 * C];
     const int tid = threadIdx.x, lane = tid & 63;
     const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -2135,21 +2169,22 @@ __device__ void fwd_lif8_pipe(const snnflow_conv_fwd_args& a, const Grid g, floa
     const __amdgpu_buffer_rsrc_t rs_y = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(a.prev_y), (short)0, (int)nbytes, 0x00020000);
     const __amdgpu_buffer_rsrc_t rs_m =
         __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(has_mem ? a.prev_mem : a.prev_y), (short)0, (int)nbytes, 0x00020000);
-    // the raw halo of tile t: 11 wave-loads of 64 x 16 B per tensor, wave w issues loads w, w + 8, w + 16
+    // the raw halo of tile t: 11 wave-loads of 64 x 16 B per tensor; wave w issues the 1-KB chunks w and
+    // w + 8 of y and of the membrane, which are the chunks its own LIF threads read (element tid + i NTB
+    // lies in chunk w + 8 i): no other wave touches them, so the wave refills them behind its own reads
     auto issue = [&](const Tile& t, int lane) {
         const int base = ((t.b * H + t.h0 - 1) * W + (t.w0 - 1)) * (C * 4);
 #pragma unroll
-        for (int j = 0; j < 3; ++j) {
-            const int k = wv + 8 * j;
-            if (k >= 22) break;
-            const bool mem = k >= 11;
-            if (mem && !has_mem) continue;
-            const int kk = mem ? k - 11 : k, ee = kk * 64 + lane, p = ee >> 1, r = p / HWD, cc = p - r * HWD;
+        for (int j = 0; j < 2; ++j) {
+            const int kk = wv + 8 * j;
+            if (kk >= 11) break;
+            const int ee = kk * 64 + lane, p = ee >> 1, r = p / HWD, cc = p - r * HWD;
             const bool ok = in_image(t.h0 + r - 1, t.w0 + cc - 1, H, W);
             const uint32_t off = ok ? (uint32_t)(base + (r * W + cc) * (C * 4) + (ee & 1) * 16) : 0x80000000u;
-            if (ee < 2 * HN)  // the last wave-load is partial: inactive lanes write no LDS
-                __builtin_amdgcn_raw_ptr_buffer_load_lds(mem ? rs_m : rs_y, (lds_void*)(lds + (mem ? L::RAWM : L::RAWY) + kk * 1024),
-                                                         16, off, 0, 0, 0);
+            if (ee < 2 * HN) {  // the last wave-load is partial: inactive lanes write no LDS
+                __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_y, (lds_void*)(lds + L::RAWY + kk * 1024), 16, off, 0, 0, 0);
+                if (has_mem) __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_m, (lds_void*)(lds + L::RAWM + kk * 1024), 16, off, 0, 0, 0);
+            }
         }
     };
     float4 rs[R];  // s_prev halo of the next tile (registers, issued one tile ahead)
@@ -2182,61 +2217,80 @@ __device__ void fwd_lif8_pipe(const snnflow_conv_fwd_args& a, const Grid g, floa
     const __bf16* rspk = reinterpret_cast<const __bf16*>(lds + L::RSPK);
     TRACE_AT(true, REC ? 1 : 0, 3);
 
+    typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
     for ([[maybe_unused]] int k = 0; v_cur >= 0; ++k) {
-        vm_wait<0>();     // this wave's DMA and s_prev loads of tile k (and its stores of tile k-1)
-        __syncthreads();  // every wave's DMA landed; every wave is done with the spike tiles of k-1
-        TRACE_AT(k < 2, REC ? 1 : 0, 4 + 3 * k);
+        vm_wait<0>();  // this wave's DMA and s_prev loads of tile k (and its stores of tile k-1)
         // the lane's tile-independent index math (halo element, DMA slot, LDS addresses) is redone per
-        // tile from an opaque copy of the thread index: hoisted out of the loop it held ~30 registers
-        const int tid = opaque_int(threadIdx.x), lane = tid & 63, jj = lane & 15, gg = lane >> 4, qt = tid & 1;
-        const LifCoef kc[4] = {coef[4 * qt], coef[4 * qt + 1], coef[4 * qt + 2], coef[4 * qt + 3]};
-        // LIF of layer l-1 over the halo (element e = pixel * 2 + channel quad, e = tid + i NTB)
+        // phase from an opaque copy of the thread index: hoisted out of the loop it held ~30 registers
+        // ---- drain: this wave's raw chunks (element e = pixel * 2 + channel quad, e = tid + i NTB) and
+        // its s_prev registers (as bf16, with their exactness) leave for registers ...
+        float4 hy[R], hm[R];
+        bf16x4 rb[R];
         bool ok = true;
+        {
+            const int tid = opaque_int(threadIdx.x);
+#pragma unroll
+            for (int i = 0; i < R; ++i) {
+                const int e = tid + i * NTB;
+                hy[i] = hm[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+                if (e < 2 * HN) {
+                    hy[i] = *reinterpret_cast<const float4*>(lds + L::RAWY + e * 16);
+                    if (has_mem) hm[i] = *reinterpret_cast<const float4*>(lds + L::RAWM + e * 16);
+                    if (has_rec) {
+                        const float4 s = rs[i];
+                        ok = ok && exact_bf16(s.x) && exact_bf16(s.y) && exact_bf16(s.z) && exact_bf16(s.w);
+                        rb[i] = bf16x4{(__bf16)s.x, (__bf16)s.y, (__bf16)s.z, (__bf16)s.w};
+                    }
+                }
+            }
+            lds_reads_done();  // ... before the DMA below may overwrite what they read
+        }
+        // ---- refill: the next tile's halo into the same chunks, a LIF phase, a barrier and the conv ahead
+        // of the wait that needs it (only this wave reads these chunks: no barrier between drain and refill)
+        const int v_nxt = v_cur + g.nb < ntiles ? v_cur + g.nb : -1;
+        const Tile cur = tl;
+        if (v_nxt >= 0) {
+            const int tid = opaque_int(threadIdx.x);
+            tl = block_tile(H, W, Grid{v_nxt, ntiles});
+            issue(tl, tid & 63);
+            if (has_rec) load_sprev(tl, tid);
+        }
+        lds_barrier();  // every wave is done with the spike tiles of k-1 (the DMA stays in flight)
+        TRACE_AT(k < 2, REC ? 1 : 0, 4 + 3 * k);
+        const int tid = opaque_int(threadIdx.x), lane = tid & 63, jj = lane & 15, gg = lane >> 4, qt = tid & 1;
+        LifCoef kc[4];
+        load_coef4(coef, qt, kc);
+        // LIF of layer l-1 over the halo
 #pragma unroll
         for (int i = 0; i < R; ++i) {
             const int e = tid + i * NTB;
             if (e < 2 * HN) {
                 const int p = e >> 1, r = p / HWD, cc = p - r * HWD;
-                const int h = tl.h0 + r - 1, w = tl.w0 + cc - 1;
-                const float4 yv = *reinterpret_cast<const float4*>(lds + L::RAWY + e * 16);
-                const float4 mv = has_mem ? *reinterpret_cast<const float4*>(lds + L::RAWM + e * 16) : make_float4(0.f, 0.f, 0.f, 0.f);
+                const int h = cur.h0 + r - 1, w = cur.w0 + cc - 1;
                 float4 sv = make_float4(0.f, 0.f, 0.f, 0.f);
                 if (in_image(h, w, H, W)) {
-                    const Lif4 o = zr ? lif_step4(yv, mv, kc, true) : lif_step4(yv, mv, kc, false);
+                    const Lif4 o = zr ? lif_step4(hy[i], hm[i], kc, true) : lif_step4(hy[i], hm[i], kc, false);
                     sv = o.s;
                     if (r >= 1 && r <= TH && cc >= 1 && cc <= TW) {
-                        const int64_t q = (((int64_t)tl.b * H + h) * W + w) * 2 + qt;
+                        const int64_t q = (((int64_t)cur.b * H + h) * W + w) * 2 + qt;
                         st_state4(st4, q, o.mout);
                         if (!spk_skip) st_state4(st4, plane4 + q, o.s);
                     }
                 }
-                typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
                 *reinterpret_cast<bf16x4*>(const_cast<__bf16*>(spk) + p * 8 + 4 * qt) =
                     bf16x4{(__bf16)sv.x, (__bf16)sv.y, (__bf16)sv.z, (__bf16)sv.w};
-                if (has_rec) {
-                    const float4 s = rs[i];
-                    ok = ok && exact_bf16(s.x) && exact_bf16(s.y) && exact_bf16(s.z) && exact_bf16(s.w);
-                    *reinterpret_cast<bf16x4*>(const_cast<__bf16*>(rspk) + p * 8 + 4 * qt) =
-                        bf16x4{(__bf16)s.x, (__bf16)s.y, (__bf16)s.z, (__bf16)s.w};
-                }
+                if (has_rec) *reinterpret_cast<bf16x4*>(const_cast<__bf16*>(rspk) + p * 8 + 4 * qt) = rb[i];
             }
         }
-        // raw halos free, spike tiles complete (and: is s_prev exact in bf16 everywhere?  A wave with an
-        // inexact value sets this tile's LDS flag -- two flags alternate over the tiles, the other one
-        // is cleared here for the next tile -- instead of __syncthreads_and's three barriers)
+        // spike tiles complete (and: is s_prev exact in bf16 everywhere?  A wave with an inexact value
+        // sets this tile's LDS flag -- two flags alternate over the tiles, the other one is cleared
+        // here for the next tile -- instead of __syncthreads_and's three barriers)
         int* const bad = slot + 2;  // pipe_slot()[2..3]
         if (has_rec && __builtin_amdgcn_ballot_w64(!ok) != 0 && lane == 0) bad[k & 1] = 1;
         if (threadIdx.x == 0) bad[(k + 1) & 1] = 0;
-        __syncthreads();
+        lds_barrier();
         const bool rec_bf = has_rec && bad[k & 1] == 0;
         TRACE_AT(k < 2, REC ? 1 : 0, 5 + 3 * k);
-        const int v_nxt = v_cur + g.nb < ntiles ? v_cur + g.nb : -1;
-        const Tile cur = tl;
-        if (v_nxt >= 0) {
-            tl = block_tile(H, W, Grid{v_nxt, ntiles});
-            issue(tl, lane);
-            if (has_rec) load_sprev(tl, tid);
-        }
 
         // conv(s) of this wave's tile row: A = fragments (rows co), B = spikes (columns: pixels)
         const bf16x8* fff = reinterpret_cast<const bf16x8*>(lds + L::FF) + gg * 8 + (jj & 7);
@@ -2343,11 +2397,11 @@ __device__ void fwd_lif8_pipe(const snnflow_conv_fwd_args& a, const Grid g, floa
 // loop around a recurrent layer cost two launches per step, stays inside the block.  LIF output is 0/1,
 // so B's recurrent conv always runs on the matrix cores (no exactness test, no s_prev registers).
 // Organised like fwd_lif8_pipe; per tile:
-//   wait(DMA A) + barrier -> LIF of layer r over the halo (state r at t-1, spikes into RSPK) -> barrier
-//   -> DMA B into the raw regions -> conv r+1 on RSPK, store y_{r+1}(t-1) -> wait(DMA B) + barrier
-//   -> LIF of layer r-1 (state r-1 at t, spikes into SPK) -> barrier -> DMA A of the next tile
-//   -> conv r on SPK + recurrent conv r on RSPK, store y_r(t).
-// Every DMA has an MFMA phase over it; RSPK is rewritten only after the next tile's first barrier.
+//   wait(DMA A) -> raw halo into registers -> DMA B into the chunks just read -> barrier -> LIF of layer r
+//   (state r at t-1, spikes into RSPK) -> barrier -> conv r+1 on RSPK, store y_{r+1}(t-1) -> wait(DMA B)
+//   -> raw halo into registers -> DMA A of the next tile -> barrier -> LIF of layer r-1 (state r-1 at t,
+//   spikes into SPK) -> barrier -> conv r on SPK + recurrent conv r on RSPK, store y_r(t).
+// Every DMA has a LIF phase and an MFMA phase over it; RSPK is rewritten only after the next tile's first barrier.
 // Each half runs its own per-block prologue and issues its own batch-sum atomics; each half's arithmetic
 // and its tiles per block are those of the task on its own (fwd_lif8_pipe).
 // ---------------------------------------------------------------------------
@@ -2369,24 +2423,23 @@ static_assert(ChainFwdLds::X_BYTES <= kSumScratch * 4 && sizeof(LifCoef) == 16 &
               "chained forward pair: fragments, coefficients and sums in the block-sum scratch");
 
 // The raw halo of tile t by LDS-DMA (fwd_lif8_pipe's issue): 11 wave-loads of 64 x 16 B per tensor,
-// wave w issues loads w, w + 8, w + 16.
+// wave w issues the chunks w and w + 8 of y and of the membrane: the chunks its own LIF threads read.
 __device__ inline void chain_issue(const __amdgpu_buffer_rsrc_t rs_y, const __amdgpu_buffer_rsrc_t rs_m, bool has_mem,
                                    char* lds, const Tile& t, int H, int W, int wv, int lane) {
     constexpr int C = 8;
     using L = ChainFwdLds;
     const int base = ((t.b * H + t.h0 - 1) * W + (t.w0 - 1)) * (C * 4);
 #pragma unroll
-    for (int j = 0; j < 3; ++j) {
-        const int k = wv + 8 * j;
-        if (k >= 22) break;
-        const bool mem = k >= 11;
-        if (mem && !has_mem) continue;
-        const int kk = mem ? k - 11 : k, ee = kk * 64 + lane, p = ee >> 1, r = p / HWD, cc = p - r * HWD;
+    for (int j = 0; j < 2; ++j) {
+        const int kk = wv + 8 * j;
+        if (kk >= 11) break;
+        const int ee = kk * 64 + lane, p = ee >> 1, r = p / HWD, cc = p - r * HWD;
         const bool ok = in_image(t.h0 + r - 1, t.w0 + cc - 1, H, W);
         const uint32_t off = ok ? (uint32_t)(base + (r * W + cc) * (C * 4) + (ee & 1) * 16) : 0x80000000u;
-        if (ee < 2 * HN)  // the last wave-load is partial: inactive lanes write no LDS
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(mem ? rs_m : rs_y, (lds_void*)(lds + (mem ? L::RAWM : L::RAWY) + kk * 1024),
-                                                     16, off, 0, 0, 0);
+        if (ee < 2 * HN) {  // the last wave-load is partial: inactive lanes write no LDS
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_y, (lds_void*)(lds + L::RAWY + kk * 1024), 16, off, 0, 0, 0);
+            if (has_mem) __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_m, (lds_void*)(lds + L::RAWM + kk * 1024), 16, off, 0, 0, 0);
+        }
     }
 }
 
@@ -2399,25 +2452,46 @@ struct ChainHalf {
     bool has_mem, zr, spk_skip;
 };
 
-// LIF of the task's previous layer over the halo from the raw regions (fwd_lif8_pipe's): the state of
-// the tile's own pixels to prev_state, the spikes as a bf16 tile to `spk`.
-__device__ inline void chain_lif(const ChainHalf& a, int B, int H, int W, const LifCoef* coef, const char* lds, __bf16* spk,
-                                 const Tile& tl, int tid) {
+// This thread's elements of the raw halo (fwd_lif8_pipe's drain): out of the raw regions into registers,
+// returned before the wave refills the chunks they came from.
+struct ChainHalo {
+    float4 y[Halo4<8, 2 * NT>::R], m[Halo4<8, 2 * NT>::R];
+};
+__device__ inline ChainHalo chain_drain(bool has_mem, const char* lds, int tid) {
     constexpr int C = 8, NTB = 2 * NT, R = Halo4<C, NTB>::R;
     using L = ChainFwdLds;
+    ChainHalo v;
+#pragma unroll
+    for (int i = 0; i < R; ++i) {
+        const int e = tid + i * NTB;
+        v.y[i] = v.m[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (e < 2 * HN) {
+            v.y[i] = *reinterpret_cast<const float4*>(lds + L::RAWY + e * 16);
+            if (has_mem) v.m[i] = *reinterpret_cast<const float4*>(lds + L::RAWM + e * 16);
+        }
+    }
+    lds_reads_done();
+    return v;
+}
+
+// LIF of the task's previous layer over the drained halo (fwd_lif8_pipe's): the state of the tile's own
+// pixels to prev_state, the spikes as a bf16 tile to `spk`.
+__device__ inline void chain_lif(const ChainHalf& a, int B, int H, int W, const LifCoef* coef, const ChainHalo& v, __bf16* spk,
+                                 const Tile& tl, int tid) {
+    constexpr int C = 8, NTB = 2 * NT, R = Halo4<C, NTB>::R;
     const int qt = tid & 1;
-    const bool has_mem = a.has_mem, zr = a.zr, spk_skip = a.spk_skip;
+    const bool zr = a.zr, spk_skip = a.spk_skip;
     const int64_t plane4 = (int64_t)B * H * W * 2;
     float4* st4 = a.st4;
-    const LifCoef kc[4] = {coef[4 * qt], coef[4 * qt + 1], coef[4 * qt + 2], coef[4 * qt + 3]};
+    LifCoef kc[4];
+    load_coef4(coef, qt, kc);
 #pragma unroll
     for (int i = 0; i < R; ++i) {
         const int e = tid + i * NTB;
         if (e < 2 * HN) {
             const int p = e >> 1, r = p / HWD, cc = p - r * HWD;
             const int h = tl.h0 + r - 1, w = tl.w0 + cc - 1;
-            const float4 yv = *reinterpret_cast<const float4*>(lds + L::RAWY + e * 16);
-            const float4 mv = has_mem ? *reinterpret_cast<const float4*>(lds + L::RAWM + e * 16) : make_float4(0.f, 0.f, 0.f, 0.f);
+            const float4 yv = v.y[i], mv = v.m[i];
             float4 sv = make_float4(0.f, 0.f, 0.f, 0.f);
             if (in_image(h, w, H, W)) {
                 const Lif4 o = zr ? lif_step4(yv, mv, kc, true) : lif_step4(yv, mv, kc, false);
@@ -2526,6 +2600,7 @@ __device__ void fwd_chain8_pipe(const conv_karg pa, const conv_karg pb, const Gr
     int v_cur = g.bid < ntiles ? g.bid : -1;  // tiles v = bid, bid + nb, ...
     if (v_cur < 0) return;
     const bool lead = g.bid == 0;
+    TRACE_AT(true, 2, 0);  // (the trace build stamps no backward kind: slot 2 is the pair's)
     const uint32_t nbytes = (uint32_t)B * H * W * C * 4;  // < 2^31 (host check)
     Tile tl = block_tile(H, W, Grid{v_cur, ntiles});
 
@@ -2562,10 +2637,12 @@ __device__ void fwd_chain8_pipe(const conv_karg pa, const conv_karg pb, const Gr
         const snnflow_conv_fwd_args a = task_args(pa);
         prologue(a, gat_a, coef[0], ha, lds + L::FA, true);
     }
+    TRACE_AT(true, 2, 1);
     {
         const snnflow_conv_fwd_args b = task_args(pb);
         prologue(b, gat_b, coef[1], hb, lds + L::FB, false);
     }
+    TRACE_AT(true, 2, 2);
 
     float sa[4] = {0.f, 0.f, 0.f, 0.f}, qa[4] = {0.f, 0.f, 0.f, 0.f};  // this lane's batch sums of A
     float sb[4] = {0.f, 0.f, 0.f, 0.f}, qb[4] = {0.f, 0.f, 0.f, 0.f};  // and of B
@@ -2575,15 +2652,15 @@ __device__ void fwd_chain8_pipe(const conv_karg pa, const conv_karg pb, const Gr
     // One copy of the tile phases, run as half A and then half B of every tile (second = 0, 1) with that
     // half's parameters: two inlined copies would double the body's code for nothing.
     Tile cur = tl;
-    for (int second = 0; v_cur >= 0; second ^= 1) {
+    TRACE_AT(true, 2, 3);
+    for ([[maybe_unused]] int k = 0, second = 0; v_cur >= 0; second ^= 1, ++k) {
         const ChainHalf hf = second ? hb : ha;
-        vm_wait<0>();     // this wave's DMA of this half (and its stores of the half before)
-        __syncthreads();  // every wave's DMA landed; every wave is done with the spike tile this half rewrites
+        vm_wait<0>();  // this wave's DMA of this half (and its stores of the half before)
         // (the lane's tile-independent index math is redone per phase from an opaque copy of the thread
         // index: hoisted out of the loop it holds ~30 registers, see fwd_lif8_pipe)
-        chain_lif(hf, B, H, W, coef[second], lds, second ? spk : rspk, cur, opaque_int(threadIdx.x));
-        __syncthreads();  // raw halos free, this half's spike tile complete
-        // the raw halo of the next half: B's of this tile, or A's of the block's next tile
+        const ChainHalo hv = chain_drain(hf.has_mem, lds, opaque_int(threadIdx.x));
+        // the raw halo of the next half into the chunks just drained (this wave's own: no barrier): B's of
+        // this tile, or A's of the block's next tile
         int v_nxt = v_cur;
         if (second) {
             v_nxt = v_cur + g.nb < ntiles ? v_cur + g.nb : -1;
@@ -2593,6 +2670,11 @@ __device__ void fwd_chain8_pipe(const conv_karg pa, const conv_karg pb, const Gr
             const ChainHalf hn = second ? ha : hb;
             chain_issue(hn.rs_y, hn.rs_m, hn.has_mem, lds, tl, H, W, wv, opaque_int(threadIdx.x) & 63);
         }
+        lds_barrier();  // every wave is done with the conv of the half before (it read the spike tile rewritten now)
+        TRACE_AT(k < 4, 2, 4 + 3 * k);
+        chain_lif(hf, B, H, W, coef[second], hv, second ? spk : rspk, cur, opaque_int(threadIdx.x));
+        lds_barrier();  // this half's spike tile complete
+        TRACE_AT(k < 4, 2, 5 + 3 * k);
         const int lane = opaque_int(threadIdx.x) & 63;
         const f32x4 yv = chain_conv(second != 0, lds + (second ? L::FB : L::FA), xlds + L::X_FR, second ? spk : rspk, rspk, wv, lane);
         const int qd = (lane >> 4) & 1, h = cur.h0 + wv, w = cur.w0 + (lane >> 5) * 16 + (lane & 15);
@@ -2613,6 +2695,7 @@ __device__ void fwd_chain8_pipe(const conv_karg pa, const conv_karg pb, const Gr
                 }
             }
         }
+        TRACE_AT(k < 4, 2, 6 + 3 * k);
         v_cur = v_nxt;
         cur = tl;
     }

@@ -26,10 +26,18 @@ KINDS = {0: ("conv_fwd", ["prologue", "lif_halo", "conv", "store+sums"]),
 
 # the forward tile pipeline (fwd_lif8_pipe, 2 tiles per block) stamps per tile; whether it runs
 # follows the library's default / SNNFLOW_PIPE_FWD (0 = one tile per block)
+FWD_KINDS = (0, 1)
 if os.environ.get("SNNFLOW_PIPE_FWD", "2") != "0":
     _P = ["gather", "coef", "frag+zero", "wait0", "lif0", "conv0", "wait1", "lif1", "conv1"]
     KINDS[0] = ("pipe_fwd", _P)
     KINDS[1] = ("pipe_fwd_rec", _P)
+    # the chained forward pair (fwd_chain8_pipe) stamps slot 2, which no backward kind of the trace build
+    # uses: both prologues, then wait / lif / conv of the first four halves (A, B of two tiles)
+    KINDS[2] = ("chain_fwd", ["prologue_a", "prologue_b", "pre", "wait_a0", "lif_a0", "conv_a0", "wait_b0", "lif_b0", "conv_b0",
+                              "wait_a1", "lif_a1", "conv_a1", "wait_b1", "lif_b1", "conv_b1"])
+    FWD_KINDS = (0, 1, 2)
+# wait*: from the y store of the phase before to the end of the phase's first barrier (the DMA wait; with
+# the halo refilled a phase earlier also the drain of the raw chunks and the issue of the refill)
 
 
 def residency(rows, t0, step_us=1.0):
@@ -68,7 +76,7 @@ def main(C=8, R=128, B=8, T=10):
     fn.argtypes = [ctypes.c_void_p, ctypes.c_size_t]
     assert fn(buf.ctypes.data, buf.nbytes) == 0
     res = {}
-    for direction, kinds in (("fwd", (0, 1)), ("bwd", (2, 3))):
+    for direction, kinds in (("fwd", FWD_KINDS), ("bwd", tuple(k for k in (2, 3) if k not in FWD_KINDS))):
         rows = {}
         for k in kinds:
             name, phases = KINDS[k]
