@@ -23,6 +23,97 @@ inline const float* spike_half(const float* state, const snnflow_firenet_plan* p
     return state + (int64_t)p->B * p->H * p->W * p->c;
 }
 
+// One time step's tensors as the backward argument builders read them; built by the caller (the
+// one-step driver from its io struct, the wavefront driver per step of its window).
+struct bwd_step {
+    const float* ys; const float* stats; const float* flow;   // the forward's [L] rows / flow
+    const float* g_flow; int64_t gflow_sb, gflow_sc;          // dL/dflow or NULL
+    float* g_cur; float* bnc;                                  // [L] rows, written
+    const float* mem_in[SNNFLOW_MAX_LAYERS];                   // incoming membranes
+    const float* g_state[SNNFLOW_MAX_LAYERS];                  // gradients of the step's output states
+    float* g_prev[SNNFLOW_MAX_LAYERS];                         // gradients of its incoming states (or NULL)
+    float* g_mem[SNNFLOW_MAX_LAYERS];                          // ... their membrane half, external states only
+    int zero_mem_half[SNNFLOW_MAX_LAYERS];                     // a recurrent layer's g_prev: zero-fill that half
+    double* acc[SNNFLOW_MAX_LAYERS];                           // backward batch-sum accumulators
+    const snnflow_neuron_grad* ng; float* g_pred_w; float* g_pred_b;
+    int accumulate;                                            // add into the neuron / pred gradients
+    float* g_x; const int64_t* gxs;                            // head input gradient (optional)
+    // weight gradients inside the tasks (optional): layers >= 1 into the plan's slabs (fused, reads
+    // s_prev), the head's (fuse_head, reads x with strides xs); wslab_accumulate stays the caller's
+    int fused, fuse_head;
+    const float* s_prev[SNNFLOW_MAX_LAYERS];
+    const float* x; const int64_t* xs;
+};
+
+// pred backward + LIF backward of layer L-1
+void fill_top_bwd(snnflow_lif_bwd_args& b, const snnflow_firenet_plan* p, const bwd_step& v) {
+    const int C = p->c, top = p->L - 1;
+    const int64_t ny = (int64_t)p->B * p->H * p->W * C;
+    memset(&b, 0, sizeof(b));
+    b.B = p->B; b.H = p->H; b.W = p->W; b.c = C;
+    b.y = v.ys + top * ny; b.mem = v.mem_in[top]; b.stats = v.stats + (int64_t)top * 2 * C; b.n = p->n[top];
+    b.g_state = v.g_state[top];
+    b.pred_w = p->pred_w; b.flow = v.flow;
+    if (v.g_flow) {
+        b.g_flow = v.g_flow; b.gflow_sb = v.gflow_sb; b.gflow_sc = v.gflow_sc;
+    }
+    b.g_cur = v.g_cur + top * ny; b.g_mem = v.g_mem[top];
+    b.acc = v.acc[top];
+}
+
+// BN backward + dgrad of layer l's convs [+ LIF backward of layer l-1]
+void fill_layer_bwd(snnflow_layer_bwd_args& a, const snnflow_firenet_plan* p, const bwd_step& v, int l) {
+    const int C = p->c;
+    const int64_t ny = (int64_t)p->B * p->H * p->W * C;
+    memset(&a, 0, sizeof(a));
+    a.B = p->B; a.H = p->H; a.W = p->W; a.c = C;
+    a.y = v.ys + l * ny; a.stats = v.stats + (int64_t)l * 2 * C; a.g_cur = v.g_cur + l * ny;
+    a.acc_in = v.acc[l];
+    a.n = p->n[l];
+    a.ng = v.ng[l];
+    a.accumulate = v.accumulate;
+    a.bnc_out = v.bnc + (int64_t)l * 2 * C;
+    if (l == p->L - 1) {
+        a.has_pred = 1; a.g_pred_w = v.g_pred_w; a.g_pred_b = v.g_pred_b;
+    }
+    if (p->rec[l]) {
+        a.wt_bwd_rec = p->wt_bwd_rec[l]; a.wt_fwd_rec = p->wt_fwd_rec[l];
+        if (v.g_prev[l]) {
+            a.g_state_prev = v.g_prev[l];
+            a.zero_mem_half = v.zero_mem_half[l];
+        }
+    }
+    a.wd_ff = p->wd_ff[l]; a.wd_rec = p->wd_rec[l];
+    if (l > 0) {
+        a.cin = C; a.lif_in = 1;
+        a.wt_bwd_ff = p->wt_bwd_ff[l]; a.wt_fwd_ff = p->wt_fwd_ff[l];
+        a.prev_y = v.ys + (l - 1) * ny; a.prev_mem = v.mem_in[l - 1];
+        a.prev_stats = v.stats + (int64_t)(l - 1) * 2 * C; a.prev = p->n[l - 1];
+        a.prev_g_state = v.g_state[l - 1];
+        a.prev_g_cur = v.g_cur + (l - 1) * ny; a.prev_g_mem = v.g_mem[l - 1];
+        a.acc_out = v.acc[l - 1];
+        if (v.fused) {
+            a.wslab_ff = p->slab_ff[l];
+            if (p->rec[l]) {
+                a.wslab_rec = p->slab_rec[l];
+                a.s_prev = v.s_prev[l];
+            }
+        }
+    } else {
+        a.cin = p->cin0; a.lif_in = 0;
+        if (v.g_x) {
+            a.wt_bwd_ff = p->wt_bwd_ff[0]; a.wt_fwd_ff = p->wt_fwd_ff[0];
+            a.g_x = v.g_x;
+            a.gxs_b = v.gxs[0]; a.gxs_c = v.gxs[1]; a.gxs_h = v.gxs[2]; a.gxs_w = v.gxs[3];
+        }
+        if (v.fuse_head) {  // ABI 40: the head's weight gradient of this step in this task
+            a.x = v.x;
+            a.xs_b = v.xs[0]; a.xs_c = v.xs[1]; a.xs_h = v.xs[2]; a.xs_w = v.xs[3];
+            a.wslab_ff = p->slab_ff[0];
+        }
+    }
+}
+
 }  // namespace
 
 extern "C" {
@@ -86,25 +177,26 @@ int snnflow_firenet_fwd(const snnflow_firenet_plan* p, const snnflow_firenet_fwd
 int snnflow_firenet_bwd(const snnflow_firenet_plan* p, const snnflow_firenet_bwd_io* io, void* stream) {
     if (check_plan(p) || !io || !io->ys || !io->stats || !io->flow || !io->g_cur || !io->bnc)
         SNN_FAIL(SNNFLOW_E_ARG, "firenet_bwd: bad arguments");
-    const int L = p->L, C = p->c, top = L - 1;
-    const int64_t npix = (int64_t)p->B * p->H * p->W;
-    const int64_t ny = npix * C;
+    const int L = p->L;
     const int zn = (int)p->bwd_acc_stride;
-    // gradients flowing into the membrane input: only for states this model did not produce
-    float* g_mem[SNNFLOW_MAX_LAYERS];
-    for (int l = 0; l < L; ++l) g_mem[l] = (io->g_prev[l] && io->ext[l]) ? io->g_prev[l] : nullptr;
-
-    snnflow_lif_bwd_args b;
-    memset(&b, 0, sizeof(b));
-    b.B = p->B; b.H = p->H; b.W = p->W; b.c = C;
-    b.y = io->ys + top * ny; b.mem = io->mem_in[top]; b.stats = io->stats + (int64_t)top * 2 * C; b.n = p->n[top];
-    b.g_state = io->g_state[top];
-    b.pred_w = p->pred_w; b.flow = io->flow;
-    if (io->g_flow) {
-        b.g_flow = io->g_flow; b.gflow_sb = io->gflow_sb; b.gflow_sc = io->gflow_sc;
+    bwd_step v;
+    memset(&v, 0, sizeof(v));
+    v.ys = io->ys; v.stats = io->stats; v.flow = io->flow;
+    v.g_flow = io->g_flow; v.gflow_sb = io->gflow_sb; v.gflow_sc = io->gflow_sc;
+    v.g_cur = io->g_cur; v.bnc = io->bnc;
+    for (int l = 0; l < L; ++l) {
+        v.mem_in[l] = io->mem_in[l]; v.g_state[l] = io->g_state[l]; v.g_prev[l] = io->g_prev[l];
+        // gradients flowing into the membrane input: only for states this model did not produce
+        v.g_mem[l] = (io->g_prev[l] && io->ext[l]) ? io->g_prev[l] : nullptr;
+        v.zero_mem_half[l] = io->ext[l] ? 0 : 1;
+        v.acc[l] = p->bwd_acc + (int64_t)l * p->bwd_acc_stride;
     }
-    b.g_cur = io->g_cur + top * ny; b.g_mem = g_mem[top];
-    b.acc = p->bwd_acc + (int64_t)top * p->bwd_acc_stride;
+    v.ng = io->ng; v.g_pred_w = io->g_pred_w; v.g_pred_b = io->g_pred_b; v.accumulate = io->accumulate;
+    v.g_x = io->g_x; v.gxs = io->gxs;
+
+    // the accumulator hand-over: the top kernel zeroes bwd_acc[0], layer l's kernel bwd_acc[l+1]
+    snnflow_lif_bwd_args b;
+    fill_top_bwd(b, p, v);
     b.zero0 = p->bwd_acc;
     b.zero_n = zn;
     int rc = snnflow_lif_bwd(&b, stream);
@@ -112,41 +204,7 @@ int snnflow_firenet_bwd(const snnflow_firenet_plan* p, const snnflow_firenet_bwd
 
     for (int l = L - 1; l >= 0; --l) {
         snnflow_layer_bwd_args a;
-        memset(&a, 0, sizeof(a));
-        a.B = p->B; a.H = p->H; a.W = p->W; a.c = C;
-        a.y = io->ys + l * ny; a.stats = io->stats + (int64_t)l * 2 * C; a.g_cur = io->g_cur + l * ny;
-        a.acc_in = p->bwd_acc + (int64_t)l * p->bwd_acc_stride;
-        a.n = p->n[l];
-        a.ng = io->ng[l];
-        a.accumulate = io->accumulate;
-        a.bnc_out = io->bnc + (int64_t)l * 2 * C;
-        if (l == L - 1) {
-            a.has_pred = 1; a.g_pred_w = io->g_pred_w; a.g_pred_b = io->g_pred_b;
-        }
-        if (p->rec[l]) {
-            a.wt_bwd_rec = p->wt_bwd_rec[l]; a.wt_fwd_rec = p->wt_fwd_rec[l];
-            if (io->g_prev[l]) {
-                a.g_state_prev = io->g_prev[l];
-                a.zero_mem_half = io->ext[l] ? 0 : 1;
-            }
-        }
-        a.wd_ff = p->wd_ff[l]; a.wd_rec = p->wd_rec[l];
-        if (l > 0) {
-            a.cin = C; a.lif_in = 1;
-            a.wt_bwd_ff = p->wt_bwd_ff[l]; a.wt_fwd_ff = p->wt_fwd_ff[l];
-            a.prev_y = io->ys + (l - 1) * ny; a.prev_mem = io->mem_in[l - 1];
-            a.prev_stats = io->stats + (int64_t)(l - 1) * 2 * C; a.prev = p->n[l - 1];
-            a.prev_g_state = io->g_state[l - 1];
-            a.prev_g_cur = io->g_cur + (l - 1) * ny; a.prev_g_mem = g_mem[l - 1];
-            a.acc_out = p->bwd_acc + (int64_t)(l - 1) * p->bwd_acc_stride;
-        } else {
-            a.cin = p->cin0; a.lif_in = 0;
-            if (io->g_x) {
-                a.wt_bwd_ff = p->wt_bwd_ff[0]; a.wt_fwd_ff = p->wt_fwd_ff[0];
-                a.g_x = io->g_x;
-                a.gxs_b = io->gxs[0]; a.gxs_c = io->gxs[1]; a.gxs_h = io->gxs[2]; a.gxs_w = io->gxs[3];
-            }
-        }
+        fill_layer_bwd(a, p, v, l);
         if (l + 1 <= L - 1) {
             a.zero0 = p->bwd_acc + (int64_t)(l + 1) * p->bwd_acc_stride;
             a.zero_n = zn;
@@ -162,7 +220,7 @@ int snnflow_firenet_bwd_seq(const snnflow_firenet_plan* p, const snnflow_firenet
     if (check_plan(p) || !q || q->T < 1 || q->T > SNNFLOW_MAX_WINDOWS || !q->bwd_acc || !q->g_cur || !q->bnc ||
         q->acc_stride < SNNFLOW_ACC_LEN(SNNFLOW_BWD_ACC(p->c)) || !slab_live)
         SNN_FAIL(SNNFLOW_E_ARG, "firenet_bwd_seq: bad arguments");
-    const int L = p->L, C = p->c, top = L - 1, K = L + 1, T = q->T;
+    const int L = p->L, C = p->c, K = L + 1, T = q->T;
     if (q->fused && C != 8) SNN_FAIL(SNNFLOW_E_ARG, "firenet_bwd_seq: fused weight gradients need c = 8");
     const int64_t npix = (int64_t)p->B * p->H * p->W;
     const int64_t ny = npix * C, nst = 2 * ny;
@@ -193,7 +251,26 @@ int snnflow_firenet_bwd_seq(const snnflow_firenet_plan* p, const snnflow_firenet
     auto s_prev = [&](int t, int l) -> const float* {
         return t == 0 ? q->s_prev0[l] : (p->rec[l] ? q->states[t - 1] + l * nst + ny : nullptr);
     };
-    auto acc_of = [&](int t, int l) { return q->bwd_acc + ((int64_t)t * L + l) * q->acc_stride; };
+    // step t's tensors as the argument builders read them
+    auto step_view = [&](int t, bwd_step& v) {
+        memset(&v, 0, sizeof(v));
+        v.ys = q->ys[t]; v.stats = q->stats[t]; v.flow = q->flow[t];
+        v.g_flow = q->g_flow[t]; v.gflow_sb = q->gflow_sb[t]; v.gflow_sc = q->gflow_sc[t];
+        v.g_cur = q->g_cur + (int64_t)t * L * ny; v.bnc = q->bnc + (int64_t)t * L * 2 * C;
+        for (int l = 0; l < L; ++l) {
+            v.mem_in[l] = mem_in(t, l); v.g_state[l] = g_st(t, l); v.g_prev[l] = g_in(t, l);
+            v.g_mem[l] = (t == 0 && q->ext0[l] && q->g_prev0[l]) ? q->g_prev0[l] : nullptr;
+            // steps t >= 1: the gradient stays inside the chain and its membrane half is never
+            // read (the cells detach the reset); step 0's leaves the chain zero-filled
+            v.zero_mem_half[l] = (t == 0 && !q->ext0[l]) ? 1 : 0;
+            v.acc[l] = q->bwd_acc + ((int64_t)t * L + l) * q->acc_stride;
+            v.s_prev[l] = s_prev(t, l);
+        }
+        v.ng = q->ng; v.g_pred_w = q->g_pred_w; v.g_pred_b = q->g_pred_b;
+        v.accumulate = (q->fresh && t == T - 1) ? 0 : 1;
+        v.fused = q->fused; v.fuse_head = q->fuse_head;
+        v.x = q->x[t]; v.xs = q->xs[t];
+    };
     for (int d = 0; d < K + 2 * (T - 1); ++d) {
         snnflow_layer_bwd_args la[SNNFLOW_MAX_SLOT_TASKS];
         snnflow_lif_bwd_args tb;
@@ -201,76 +278,20 @@ int snnflow_firenet_bwd_seq(const snnflow_firenet_plan* p, const snnflow_firenet
         bool has_top = false;
         for (int j = 0; j < K; ++j) {
             if ((d - j) % 2 || (d - j) < 0 || (d - j) / 2 >= T) continue;
-            const int t = T - 1 - (d - j) / 2;
-            const float* ys = q->ys[t];
-            const float* stats = q->stats[t];
-            float* gcur = q->g_cur + (int64_t)t * L * ny;
-            auto g_mem = [&](int l) -> float* { return (t == 0 && q->ext0[l] && q->g_prev0[l]) ? q->g_prev0[l] : nullptr; };
-            if (j == 0) {  // pred backward + LIF backward of layer L-1
-                snnflow_lif_bwd_args& b = tb;
-                memset(&b, 0, sizeof(b));
-                b.B = p->B; b.H = p->H; b.W = p->W; b.c = C;
-                b.y = ys + top * ny; b.mem = mem_in(t, top); b.stats = stats + (int64_t)top * 2 * C; b.n = p->n[top];
-                b.g_state = g_st(t, top);
-                b.pred_w = p->pred_w; b.flow = q->flow[t];
-                if (q->g_flow[t]) {
-                    b.g_flow = q->g_flow[t]; b.gflow_sb = q->gflow_sb[t]; b.gflow_sc = q->gflow_sc[t];
-                }
-                b.g_cur = gcur + top * ny; b.g_mem = g_mem(top);
-                b.acc = acc_of(t, top);
+            bwd_step v;
+            step_view(T - 1 - (d - j) / 2, v);
+            if (j == 0) {
+                fill_top_bwd(tb, p, v);
                 has_top = true;
                 continue;
             }
             const int l = L - j;
             if (nl == SNNFLOW_MAX_SLOT_TASKS) SNN_FAIL(SNNFLOW_E_ARG, "firenet_bwd_seq: too many layers for a launch");
             snnflow_layer_bwd_args& a = la[nl++];
-            memset(&a, 0, sizeof(a));
-            a.B = p->B; a.H = p->H; a.W = p->W; a.c = C;
-            a.y = ys + l * ny; a.stats = stats + (int64_t)l * 2 * C; a.g_cur = gcur + l * ny;
-            a.acc_in = acc_of(t, l);
-            a.n = p->n[l];
-            a.ng = q->ng[l];
-            a.accumulate = (q->fresh && t == T - 1) ? 0 : 1;
-            a.bnc_out = q->bnc + ((int64_t)t * L + l) * 2 * C;
-            if (l == L - 1) {
-                a.has_pred = 1; a.g_pred_w = q->g_pred_w; a.g_pred_b = q->g_pred_b;
-            }
-            if (p->rec[l]) {
-                a.wt_bwd_rec = p->wt_bwd_rec[l]; a.wt_fwd_rec = p->wt_fwd_rec[l];
-                if (float* gp = g_in(t, l)) {
-                    a.g_state_prev = gp;
-                    // steps t >= 1: the gradient stays inside the chain and its membrane half is never
-                    // read (the cells detach the reset); step 0's leaves the chain zero-filled
-                    a.zero_mem_half = (t == 0 && !q->ext0[l]) ? 1 : 0;
-                }
-            }
-            a.wd_ff = p->wd_ff[l]; a.wd_rec = p->wd_rec[l];
-            if (l > 0) {
-                a.cin = C; a.lif_in = 1;
-                a.wt_bwd_ff = p->wt_bwd_ff[l]; a.wt_fwd_ff = p->wt_fwd_ff[l];
-                a.prev_y = ys + (l - 1) * ny; a.prev_mem = mem_in(t, l - 1);
-                a.prev_stats = stats + (int64_t)(l - 1) * 2 * C; a.prev = p->n[l - 1];
-                a.prev_g_state = g_st(t, l - 1);
-                a.prev_g_cur = gcur + (l - 1) * ny; a.prev_g_mem = g_mem(l - 1);
-                a.acc_out = acc_of(t, l - 1);
-                if (q->fused) {
-                    a.wslab_ff = p->slab_ff[l];
-                    if (p->rec[l]) {
-                        a.wslab_rec = p->slab_rec[l];
-                        a.s_prev = s_prev(t, l);
-                    }
-                    a.wslab_accumulate = slab_live[l] ? 1 : 0;
-                    slab_live[l] = 1;
-                }
-            } else {
-                a.cin = p->cin0; a.lif_in = 0;
-                if (q->fuse_head) {  // ABI 40: the head's weight gradient of step t in this task
-                    a.x = q->x[t];
-                    a.xs_b = q->xs[t][0]; a.xs_c = q->xs[t][1]; a.xs_h = q->xs[t][2]; a.xs_w = q->xs[t][3];
-                    a.wslab_ff = p->slab_ff[0];
-                    a.wslab_accumulate = slab_live[0] ? 1 : 0;
-                    slab_live[0] = 1;
-                }
+            fill_layer_bwd(a, p, v, l);
+            if (l > 0 ? q->fused : q->fuse_head) {  // the task adds its weight gradient to the layer's slab rows
+                a.wslab_accumulate = slab_live[l] ? 1 : 0;
+                slab_live[l] = 1;
             }
         }
         const int rc = snnflow_bwd_slot(la, nl, has_top ? &tb : nullptr, stream);

@@ -18,7 +18,7 @@ import torch.nn as nn
 from . import _lib
 from ._lib import check, lib, ptr
 from .engine import (Workspace, _ptr_t, _x_strides, as_nhwc_state, empty_state,
-                     neuron_struct, theta_subtract)
+                     neuron_struct, theta_subtract, zeros_state)
 from .norm import MPBN, TEBN, MPBNStateFn, PointwiseFn
 
 
@@ -365,8 +365,7 @@ class CellFn(torch.autograd.Function):
         b.mem_grad_in = 1 if (gst is not None and not cell.detach) else 0
         g_prev = None
         if ctx.has_prev and ctx.needs_input_grad[2]:
-            g_prev = torch.zeros((2, B, C, H, W), device=dev).as_strided(
-                (2, B, C, H, W), (B * H * W * C, H * W * C, 1, W * C, C))
+            g_prev = zeros_state(B, C, H, W, dev)
             b.g_mem = ptr(g_prev)
         b.g_cur, b.acc = ptr(g_cur), ptr(bacc)
         _lib.call("lif_bwd", lib.snnflow_lif_bwd, ctypes.byref(b), s)

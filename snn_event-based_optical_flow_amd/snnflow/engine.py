@@ -15,6 +15,7 @@ gradients in per-block slabs, neuron/BN gradients in place) and returned once,
 by the first step of the window ("root"), so autograd performs no per-step
 gradient additions.
 """
+import collections
 import ctypes
 import operator
 import os
@@ -23,7 +24,8 @@ import torch
 
 from . import _lib
 from ._lib import check, lib, ptr
-
+# (FireNetSequence resolves the schedulers through this module's globals: tests and tools wrap them here)
+from .schedule import chainable_layers, chained_bwd_slots, chained_fwd_slots, wavefront_slots  # noqa: F401
 
 
 def nhwc_state_strides(B, C, H, W):
@@ -33,6 +35,10 @@ def nhwc_state_strides(B, C, H, W):
 
 def empty_state(B, C, H, W, device):
     return torch.empty_strided((2, B, C, H, W), nhwc_state_strides(B, C, H, W), device=device, dtype=torch.float32)
+
+
+def zeros_state(B, C, H, W, device):
+    return torch.zeros((2, B, C, H, W), device=device).as_strided((2, B, C, H, W), nhwc_state_strides(B, C, H, W))
 
 
 def as_nhwc_state(s):
@@ -445,11 +451,23 @@ class FireNetEngine:
         (autograd.grad / backward(inputs=...) on an intermediate state) is abandoned: its partial weight
         gradients and pending steps would otherwise be added to this pass's."""
         if self.bwd_open and getattr(self, "bwd_task", None) != torch._C._current_graph_task_id():
-            if self.ws is not None:
-                self.ws.reset_acc()
-            self.bwd_open = False
-            self.pending, self.pending_layers = [], []
-            self.prep_stale = True
+            self.abort_backward()
+
+    def abort_backward(self):
+        """A backward failed or was abandoned: the accumulators back to zero, the chain closed, its
+        pending steps dropped, the weights re-prepared at the next forward."""
+        if self.ws is not None:
+            self.ws.reset_acc()
+        self.bwd_open = False
+        self.pending, self.pending_layers = [], []
+        self.prep_stale = True
+
+    def close_chain(self):
+        """The chain's first step is done: its flat gradient buffer goes to autograd."""
+        self.flat_views = None
+        self.bwd_open = False
+        self.last_flat = self.flat
+        self.prep_stale = True
 
     def launch_wgrad(self, l, B, H, W, cin0, ws, stream, steps=None):
         """Deferred weight gradients of layer l over the given pending time steps (default: all;
@@ -469,21 +487,21 @@ class FireNetEngine:
             a.exact_inputs = 1 if l > 0 else 0
             a.bn_weight = ptr(self.cells[l].bn.weight)
             a.slab_ff, a.slab_rec = ptr(ws.slab_ff[l]), _ptr_t(ws.slab_rec[l])
-            for k, (gcur, bnc, ys, stats, x, states, s_prev, _, bits) in enumerate(chunk):
+            for k, e in enumerate(chunk):
                 st = a.steps[k]
-                st.g_cur, st.y, st.stats, st.bnc = gcur[l], ys[l], stats[l], bnc[l]
-                xb, sb = bits if bits is not None else (None, None)
+                st.g_cur, st.y, st.stats, st.bnc = e.g_cur[l], e.ys[l], e.stats[l], e.bnc[l]
+                xb, sb = e.bits if e.bits is not None else (None, None)
                 if l == 0:
-                    st.x = ptr(x)
-                    st.xs_b, st.xs_c, st.xs_h, st.xs_w = _x_strides(x)
+                    st.x = ptr(e.x)
+                    st.xs_b, st.xs_c, st.xs_h, st.xs_w = _x_strides(e.x)
                 elif xb is not None and xb[l - 1] is not None:  # layer l-1's spikes as a bit plane (ABI 39)
                     st.x_bits = xb[l - 1]
                 else:
-                    st.x, (st.xs_b, st.xs_c, st.xs_h, st.xs_w) = _spk_half(states[l - 1])
+                    st.x, (st.xs_b, st.xs_c, st.xs_h, st.xs_w) = _spk_half(e.states[l - 1])
                 if rec and sb is not None and sb[l] is not None:
                     st.s_prev_bits = sb[l]
                 else:
-                    st.s_prev = _ptr_t(s_prev[l]) if rec else None
+                    st.s_prev = _ptr_t(e.s_prev[l]) if rec else None
             _lib.call(f"wgrad[{l}]", lib.snnflow_wgrad, ctypes.byref(a), stream)
             self.slab_live[l] = True
 
@@ -614,6 +632,41 @@ class _Rows:
 
 def _rows(t):
     return t if isinstance(t, _Rows) else _Rows(t)
+
+
+# One time step of an open backward chain as the deferred weight gradients read it (engine.pending):
+# row pointers (_Rows) of the step's g_cur / bnc / ys / stats, its input, states and previous spikes,
+# `keep` the tensors behind the pointers, `bits` the (x, s_prev) spike bit planes per layer or None.
+Pending = collections.namedtuple("Pending", "g_cur bnc ys stats x states s_prev keep bits")
+
+
+def _flow_grad(g, W):
+    """dL/dflow as the kernels read it (fp32, unit W stride, rows W apart), or None."""
+    if g is not None and (g.stride(3) != 1 or g.stride(2) != W or g.dtype != torch.float32):
+        g = g.contiguous().float()
+    return g
+
+
+def _fuse_head_ok(eng, cin0, xs):
+    """The head's weight gradient inside its backward tasks (ABI 40): a feed-forward 2- / 4-channel head."""
+    return (bool(eng.fuse_head) and not eng.rec[0] and cin0 in (2, 4)
+            and all(x.dim() == 4 and x.dtype == torch.float32 for x in xs))
+
+
+def _state_input_grads(eng, has_prev, needs, ext, B, H, W, dev):
+    """Gradient buffers of a step's incoming states (needs[l]: autograd wants layer l's): the spike
+    half of a recurrent cell's (rec dgrad); for a state this engine did not produce also the membrane
+    half (v depends on the incoming membrane, SNNtorch_spiking_submodules.py:305 / snn.Leaky), so that
+    one starts zeroed.  None elsewhere."""
+    g = [None] * eng.L
+    for l in range(eng.L):
+        if not (has_prev[l] and needs[l]):
+            continue
+        if ext[l]:
+            g[l] = zeros_state(B, eng.C, H, W, dev)
+        elif eng.rec[l]:
+            g[l] = empty_state(B, eng.C, H, W, dev)
+    return g
 
 
 def theta_subtract(cell, g_cur, mem, npix, g_theta, stream):
@@ -1004,22 +1057,13 @@ def _chain_backward_batched(eng, steps):
     buf = torch.empty(ng_ + nb_ + no_, device=dev)
     gcur, bnc = buf[:ng_].view(T, L, B, H, W, C), buf[ng_:ng_ + nb_].view(T, L, 2, C)
     bacc = torch.zeros(T * L * nacc, dtype=torch.float64, device=dev)
-    g0 = [None] * L
-    for l in range(L):
-        if not (first.has_prev[l] and first.needs[2 + l]):
-            continue
-        if first.ext[l]:
-            g0[l] = torch.zeros((2, B, C, H, W), device=dev).as_strided(
-                (2, B, C, H, W), (B * H * W * C, H * W * C, 1, W * C, C))
-        elif eng.rec[l]:
-            g0[l] = empty_state(B, C, H, W, dev)
+    g0 = _state_input_grads(eng, first.has_prev, first.needs[2:2 + L], first.ext, B, H, W, dev)
     q = _lib.FireNetSeqBwd()
     q.T, q.fresh = T, 1 if fresh else 0
     fuse = bool(eng.fuse_wgrad) and C == 8
     q.fused = 1 if fuse else 0
     xs0 = [st.saved[0] for st in steps]
-    fuse_head = (bool(eng.fuse_head) and not eng.rec[0] and cin0 in (2, 4)
-                 and all(x.dim() == 4 and x.dtype == torch.float32 for x in xs0))
+    fuse_head = _fuse_head_ok(eng, cin0, xs0)
     q.fuse_head = 1 if fuse_head else 0
     if fuse_head:
         for t, x in enumerate(xs0):
@@ -1031,10 +1075,8 @@ def _chain_backward_batched(eng, steps):
     q.states[:T] = [st.saved[4].data_ptr() for st in steps]  # (the step's L states: one allocation)
     gfl = []
     for t, st in enumerate(steps):
-        g = st.g_flow
+        g = _flow_grad(st.g_flow, W)
         if g is not None:
-            if g.stride(3) != 1 or g.stride(2) != W or g.dtype != torch.float32:
-                g = g.contiguous().float()
             q.g_flow[t], q.gflow_sb[t], q.gflow_sc[t] = g.data_ptr(), g.stride(0), g.stride(1)
         gfl.append(g)
     mem0, sp0 = first.ptrs
@@ -1061,21 +1103,15 @@ def _chain_backward_batched(eng, steps):
         for t in range(T - 1, -1, -1):
             st = steps[t]
             x, ys, stats = st.saved[:3]
-            eng.pending.append((_Rows(gcur[t]), _Rows(bnc[t]), _Rows(ys), _Rows(stats), x, st.saved[4:4 + L],
-                                st.ptrs[1], (st.saved, buf), None))
+            eng.pending.append(Pending(_Rows(gcur[t]), _Rows(bnc[t]), _Rows(ys), _Rows(stats), x, st.saved[4:4 + L],
+                                       st.ptrs[1], (st.saved, buf), None))
             eng.pending_layers.append(tuple(l for l in range(L) if not ((fuse and l > 0) or (fuse_head and l == 0))))
         eng.flush_weight_grads(B, H, W, cin0, ws, glayers, s, plan)
     except Exception:
-        eng.ws.reset_acc()
-        eng.bwd_open = False
-        eng.pending, eng.pending_layers = [], []
-        eng.prep_stale = True
+        eng.abort_backward()
         raise
     g_anchor = eng.flat if first.needs[2 + L] else None
-    eng.flat_views = None
-    eng.bwd_open = False
-    eng.last_flat = eng.flat
-    eng.prep_stale = True
+    eng.close_chain()
     del gfl
     return (None, None, *g0, g_anchor)
 
@@ -1108,18 +1144,7 @@ def _step_backward(eng, ctx, g_states=None):
     bacc = _Rows(ws.bwd_acc)
     zn = ws.bwd_acc.shape[1]
     gst = [as_nhwc_state(g) if g is not None else None for g in g_states]
-    # gradients of the previous states: the spike half of recurrent cells (rec dgrad);
-    # for states that did not come from this engine also the membrane half
-    # (v depends on the incoming membrane, SNNtorch_spiking_submodules.py:305 / snn.Leaky).
-    g_prev = [None] * L
-    for l in range(L):
-        if not (ctx.has_prev[l] and ctx.needs[2 + l]):
-            continue
-        if ctx.ext[l]:
-            g_prev[l] = torch.zeros((2, B, C, H, W), device=dev).as_strided(
-                (2, B, C, H, W), (B * H * W * C, H * W * C, 1, W * C, C))
-        elif eng.rec[l]:
-            g_prev[l] = empty_state(B, C, H, W, dev)
+    g_prev = _state_input_grads(eng, ctx.has_prev, ctx.needs[2:2 + L], ctx.ext, B, H, W, dev)
     gmem = [g_prev[l] if (g_prev[l] is not None and ctx.ext[l]) else None for l in range(L)]
 
     # per-step buffers kept until the deferred weight gradients run (root step)
@@ -1127,14 +1152,13 @@ def _step_backward(eng, ctx, g_states=None):
     bnc_t = torch.empty(L, 2, C, device=dev)           # BN backward coefficients (grad_mean, k)
     gcur, bnc, ys, stats = _Rows(gcur_t), _Rows(bnc_t), _Rows(ys), _Rows(stats)
     # pending: row pointers for the deferred wgrad + the tensors behind them (kept alive)
-    eng.pending.append((gcur, bnc, ys, stats, x, states, s_prev, (keep, gcur_t, bnc_t, saved), None))
+    eng.pending.append(Pending(gcur, bnc, ys, stats, x, states, s_prev, (keep, gcur_t, bnc_t, saved), None))
     eng.pending_layers.append(tuple(range(L)))
     # (the deferred weight gradients stay on this stream after the chain: a side stream
     # overlapping them with the root step's chain measured slower under graph replay,
     # 2.48 -> 2.72 ms per cfg2 train step)
     try:
-        if g_flow is not None and (g_flow.stride(3) != 1 or g_flow.stride(2) != W or g_flow.dtype != torch.float32):
-            g_flow = g_flow.contiguous().float()
+        g_flow = _flow_grad(g_flow, W)
         gx = None
         if ctx.needs[1]:
             gx = torch.empty_like(x)
@@ -1173,10 +1197,7 @@ def _step_backward(eng, ctx, g_states=None):
         if ctx.root:
             eng.flush_weight_grads(B, H, W, cin0, ws, glayers, s, plan)
     except Exception:
-        ws.reset_acc()
-        eng.bwd_open = False
-        eng.pending, eng.pending_layers = [], []
-        eng.prep_stale = True
+        eng.abort_backward()
         raise
 
     g_anchor = None
@@ -1184,10 +1205,7 @@ def _step_backward(eng, ctx, g_states=None):
         # the whole flat gradient buffer to the chain's parameter anchor (ParamAnchor splits it
         # into per-parameter views once every step of the chain is done)
         g_anchor = eng.flat if ctx.needs[2 + L] else None
-        eng.flat_views = None
-        eng.bwd_open = False
-        eng.last_flat = eng.flat
-        eng.prep_stale = True
+        eng.close_chain()
     return (None, gx, *g_prev, g_anchor)
 
 
@@ -1201,171 +1219,65 @@ def _ptr_t(t):
 # ---------------------------------------------------------------------------
 # A whole truncated-BPTT window in one autograd node, launched in wavefront order
 # ---------------------------------------------------------------------------
-def wavefront_slots(T, K):
-    """Launch order of a (kernel k < K, step t < T) grid whose task (k, t) reads the outputs of
-    (k-1, t), (k, t-1) and (k+1, t-1) (the spikes of a recurrent layer come out of the next
-    kernel of the previous step): task (k, t) runs in launch k + 2t, so every launch holds
-    mutually independent tasks and follows all of its inputs' launches.
-    Returns [[(k, t), ...] per launch]."""
-    slots = [[] for _ in range(K + 2 * (T - 1))]
-    for t in range(T):
-        for k in range(K):
-            slots[k + 2 * t].append((k, t))
-    return slots
+def _same_shape_inputs(xs):
+    """(B, cin0, H, W) of a window's inputs: fp32 device tensors of one shape."""
+    shape = tuple(xs[0].shape)
+    for x in xs:
+        _lib.require_device(x, "event tensor")
+        if tuple(x.shape) != shape:
+            raise _lib.SnnflowError("forward_sequence: every step's input must have the same shape")
+    return shape
 
 
-def chainable_layers(rec):
-    """Recurrent layers r whose backward task (r, t+1) can run chained to task (r+1, t): r is LIF-fed
-    (not the head), layer r+1 is a feed-forward layer below the top (its task consumes the gradient of
-    r's spikes; for the last layer the top task does, and an adjacent recurrent layer r+1 would close a
-    second loop through the same block)."""
-    L = len(rec)
-    return [r for r in range(1, L - 1) if rec[r] and not rec[r + 1]]
-
-
-def chained_bwd_slots(T, rec, chain=(), max_tasks=_lib.MAX_CHAIN_TASKS):
-    """Launches of the backward of a T-step window over layers 0..L-1 (rec[l]: recurrent); task (k, t)
-    is the backward task of layer k at step t, (L, t) the top task.  Task (k, t) follows
-      (k+1, t)    g_cur and the BatchNorm-backward sums of layer k,
-      (k, t+1)    the same layer's later step (parameter gradients and slab rows are read-modify-write
-                  in descending t, so one layer's tasks sit in distinct launches in that order),
-      (k-1, t+1)  where layer k-1 is recurrent: the gradient of its spikes at step t.
-    For r in `chain` the tasks (r, t+1) and (r+1, t) form one node, a chained pair run by one block per
-    tile (snnflow_bwd_chain): the third dependency stays inside the node, so the loop around layer r
-    costs one launch per step, not two.  A node goes into the launch after its latest dependency (its
-    longest-path level: the same-layer order skews the steps into a wavefront, so the launches fill
-    evenly), or the next one with room for its tasks (max_tasks layer tasks per launch).
-    Returns [[node, ...] per launch], node = ((k, t),) or ((r, t+1), (r+1, t)), layers descending."""
-    L = len(rec)
-    chain = set(chain)
-    if not all(1 <= r < L - 1 and rec[r] and not rec[r + 1] for r in chain):
-        raise ValueError("chained_bwd_slots: a chained layer is recurrent, LIF-fed and followed by a feed-forward layer")
-    node_of = {}
-    for k in range(L + 1):
-        for t in range(T):
-            if k in chain and t >= 1:
-                node = ((k, t), (k + 1, t - 1))
-            elif k - 1 in chain and t <= T - 2:
-                node = ((k - 1, t + 1), (k, t))
-            else:
-                node = ((k, t),)
-            node_of[(k, t)] = node
-
-    def deps(node):
-        out = set()
-        for k, t in node:
-            if k < L:
-                out.add((k + 1, t))
-            if t + 1 < T:
-                out.add((k, t + 1))
-                if k >= 1 and rec[k - 1]:
-                    out.add((k - 1, t + 1))
-        return {node_of[d] for d in out if d not in node}
-
-    level = {}
-
-    def lvl(node):  # longest path from a source (depth <= T + L nodes)
-        if node not in level:
-            level[node] = 1 + max((lvl(d) for d in deps(node)), default=-1)
-        return level[node]
-
-    nodes = sorted(set(node_of.values()), key=lambda n: (lvl(n), -n[0][0], -n[0][1]))
-    slot, fill, launches = {}, [], []
-    for n in nodes:
-        s = 1 + max((slot[d] for d in deps(n)), default=-1)
-        nl = sum(1 for k, _ in n if k < L)
-        while s < len(fill) and fill[s] + nl > max_tasks:
-            s += 1
-        while len(launches) <= s:
-            launches.append([])
-            fill.append(0)
-        slot[n] = s
-        fill[s] += nl
-        launches[s].append(n)
-    for la in launches:
-        la.sort(key=lambda n: -n[0][0])
-    return launches
-
-
-def chained_fwd_slots(T, rec, chain=(), max_tasks=_lib.MAX_CHAIN_TASKS):
-    """Launches of the forward of a T-step window over layers 0..L-1 (rec[l]: recurrent); task (k, t)
-    is the forward task of layer k at step t (the LIF of layer k-1 on the halo + the convs of layer k),
-    (L, t) the top task.  Task (k, t) follows
-      (k-1, t)    the pre-BN current of layer k-1 and its batch statistics,
-      (k, t-1)    the same layer's earlier step (membrane of layer k-1, running statistics; kept for the
-                  head too, so that the steps skew into an even wavefront),
-      (k+1, t-1)  where layer k is recurrent: its spikes of step t-1, computed by the next layer's task.
-    For r in `chain` the tasks (r+1, t-1) and (r, t) form one node, a chained pair run by one block per
-    tile (snnflow_fwd_chain): the third dependency stays inside the node, so the loop around layer r
-    costs one launch per step, not two.  Step 0's task of layer r and task (r+1, T-1) stay single.  A
-    node goes into the launch after its latest dependency (its longest-path level), or the next one
-    with room for its tasks (max_tasks conv tasks per launch).
-    Returns [[node, ...] per launch], node = ((k, t),) or ((r+1, t-1), (r, t)), layers ascending."""
-    L = len(rec)
-    chain = set(chain)
-    if not all(1 <= r < L - 1 and rec[r] and not rec[r + 1] for r in chain):
-        raise ValueError("chained_fwd_slots: a chained layer is recurrent, LIF-fed and followed by a feed-forward "
-                         "layer below the top")
-    node_of = {}
-    for k in range(L + 1):
-        for t in range(T):
-            if k in chain and t >= 1:
-                node = ((k + 1, t - 1), (k, t))
-            elif k - 1 in chain and t <= T - 2:
-                node = ((k, t), (k - 1, t + 1))
-            else:
-                node = ((k, t),)
-            node_of[(k, t)] = node
-
-    def deps(node):
-        out = set()
-        for k, t in node:
-            if k >= 1:
-                out.add((k - 1, t))
-            if t >= 1:
-                out.add((k, t - 1))
-                if k < L and rec[k]:
-                    out.add((k + 1, t - 1))
-        return {node_of[d] for d in out if d not in node}
-
-    level = {}
-
-    def lvl(node):  # longest path from a source (depth <= T + L nodes)
-        if node not in level:
-            level[node] = 1 + max((lvl(d) for d in deps(node)), default=-1)
-        return level[node]
-
-    nodes = sorted(set(node_of.values()), key=lambda n: (lvl(n), min(k for k, _ in n), n[0][1]))
-    slot, fill, launches = {}, [], []
-    for n in nodes:
-        s = 1 + max((slot[d] for d in deps(n)), default=-1)
-        nl = sum(1 for k, _ in n if k < L)
-        while s < len(fill) and fill[s] + nl > max_tasks:
-            s += 1
-        while len(launches) <= s:
-            launches.append([])
-            fill.append(0)
-        slot[n] = s
-        fill[s] += nl
-        launches[s].append(n)
-    for la in launches:
-        la.sort(key=lambda n: min(k for k, _ in n))
-    return launches
-
-
-def _state_rows(st_all, fin, T):
-    """Flat per-step state rows of a FireNetSequence call: st_all's rows, the last one replaced by
-    the caller's final_state_out buffer when there is one (st_all then has T - 1 rows)."""
+def _state_views(eng, st_all, fin, T, B, H, W):
+    """(rows, states) of a window's state storage: the flat per-step rows -- st_all's, the last one
+    replaced by the caller's final_state_out buffer when there is one (st_all then has T - 1 rows) --
+    and states[t][l], layer l's [2, B, C, H, W] state of step t as a view into row t."""
+    L, C = eng.L, eng.C
+    n1 = 2 * B * H * W * C
     rows = [st_all[t] for t in range(st_all.shape[0])]
-    return rows + [fin] if fin is not None else rows
+    if fin is not None:
+        rows.append(fin)
+    sst = nhwc_state_strides(B, C, H, W)
+    states = [[rows[t][l * n1:(l + 1) * n1].as_strided((2, B, C, H, W), sst) for l in range(L)] for t in range(T)]
+    return rows, states
+
+
+def _window_states(eng, T, B, H, W, dev, prev):
+    """Allocates a window's state storage; takes (and clears) the engine's one-shot final_state_out.
+    Returns (st_all, fin, rows, states), the last two as _state_views gives them."""
+    n = eng.L * 2 * B * H * W * eng.C
+    fin = eng.final_state_out
+    eng.final_state_out = None
+    if fin is not None:
+        if (fin.device != dev or fin.dtype != torch.float32 or fin.numel() != n or not fin.is_contiguous()
+                or any(p is not None and p.untyped_storage().data_ptr() == fin.untyped_storage().data_ptr()
+                       for p in prev)):
+            raise _lib.SnnflowError("final_state_out: a contiguous fp32 buffer of L*2*B*H*W*C floats on the "
+                                    "input's device, not aliasing the initial states")
+        fin = fin.view(n)
+    st_all = torch.empty(T - (fin is not None), n, device=dev)
+    return (st_all, fin, *_state_views(eng, st_all, fin, T, B, H, W))
+
+
+def _slot_call(name, chain_fn, slot_fn, chained, arg_type, tasks, pairs, top, stream):
+    """One wavefront launch: `tasks` (arg_type structs) and the optional top task through slot_fn, or,
+    on a chained schedule, through chain_fn with the pair flags (pairs[i] = 1: task i hands over to i + 1)."""
+    arr = (arg_type * max(len(tasks), 1))(*tasks)
+    top = ctypes.byref(top) if top is not None else None
+    if chained:
+        _lib.call(name, chain_fn, arr, len(tasks), (ctypes.c_ubyte * max(len(pairs), 1))(*pairs), top, stream)
+    else:
+        _lib.call(name, slot_fn, arr, len(tasks), top, stream)
 
 
 class FireNetSequence(torch.autograd.Function):
     """T fused time steps of the network as one autograd node (``forward_sequence``).
 
     Same arithmetic per (layer, step) as T FireNetStep calls; the L+1 kernels of every step are
-    issued as wavefront launches (``wavefront_slots``, ``snnflow_fwd_slot`` /
-    ``snnflow_bwd_slot``) that each run up to four independent layer-steps: a single
+    issued as wavefront launches (``wavefront_slots``, ``snnflow_fwd_slot`` / ``snnflow_bwd_slot``;
+    the schedulers live in ``snnflow/schedule.py`` and are called through this module's globals)
+    that each run up to four independent layer-steps: a single
     layer-step of C = 8 at 128x128 occupies the chip for one latency-bound block round, so
     the (L+1) x T launches of the per-step path are replaced by 2(T-1)+L+1.  The forward at C = 8 runs
     the chained schedule (``chained_fwd_slots``, ``snnflow_fwd_chain``): the task that computes a
@@ -1380,12 +1292,8 @@ class FireNetSequence(torch.autograd.Function):
         L, C = eng.L, eng.C
         xs = list(rest[:T])
         prev = list(rest[T:T + L])
-        B, cin0, H, W = xs[0].shape
+        B, cin0, H, W = _same_shape_inputs(xs)
         dev = xs[0].device
-        for x in xs:
-            _lib.require_device(x, "event tensor")
-            if tuple(x.shape) != (B, cin0, H, W):
-                raise _lib.SnnflowError("forward_sequence: every step's input must have the same shape")
         s = _lib.stream_ptr(dev)
         ws = eng.workspace(B, H, W, dev)
         # the batch-sum accumulators of this forward (facc) and of its backward (bacc), one fp64
@@ -1400,20 +1308,7 @@ class FireNetSequence(torch.autograd.Function):
 
         ys = torch.empty(T, L, B, H, W, C, device=dev)
         stats = torch.empty(T, L, 2, C, device=dev)
-        n1 = 2 * B * H * W * C
-        fin = eng.final_state_out
-        eng.final_state_out = None
-        if fin is not None:
-            if (fin.device != dev or fin.dtype != torch.float32 or fin.numel() != L * n1 or not fin.is_contiguous()
-                    or any(p is not None and p.untyped_storage().data_ptr() == fin.untyped_storage().data_ptr()
-                           for p in prev)):
-                raise _lib.SnnflowError("final_state_out: a contiguous fp32 buffer of L*2*B*H*W*C floats on the "
-                                        "input's device, not aliasing the initial states")
-            fin = fin.view(L * n1)
-        st_all = torch.empty(T - (fin is not None), L * n1, device=dev)
-        rows = _state_rows(st_all, fin, T)
-        states = [[rows[t][l * n1:(l + 1) * n1].as_strided((2, B, C, H, W), nhwc_state_strides(B, C, H, W))
-                   for l in range(L)] for t in range(T)]
+        st_all, fin, _, states = _window_states(eng, T, B, H, W, dev, prev)
         flows = [torch.empty(B, 2, H, W, device=dev) for _ in range(T)]
 
         # step 0 reads the initial states (as FireNetStep); step t > 0 the states of step t-1
@@ -1497,14 +1392,8 @@ class FireNetSequence(torch.autograd.Function):
                                         flows[t])
                     if spk_skip(L - 1, t):
                         top.state_spk_skip = 1
-            arr = (_lib.ConvFwdArgs * max(len(convs), 1))(*convs)
-            if chained:
-                _lib.call("fwd_slot", lib.snnflow_fwd_chain, arr, len(convs),
-                          (ctypes.c_ubyte * max(len(pairs), 1))(*pairs),
-                          ctypes.byref(top) if top is not None else None, s)
-            else:
-                _lib.call("fwd_slot", lib.snnflow_fwd_slot, arr, len(convs),
-                          ctypes.byref(top) if top is not None else None, s)
+            _slot_call("fwd_slot", lib.snnflow_fwd_chain, lib.snnflow_fwd_slot, chained, _lib.ConvFwdArgs, convs, pairs,
+                       top, s)
         _lib.timer_close()
 
         if eng.capture_states:  # tests / diagnostics: the window's pre-BN currents, statistics, batch sums
@@ -1545,10 +1434,7 @@ class FireNetSequence(torch.autograd.Function):
         ys, stats, st_all = saved[2 * T:2 * T + 3]
         rest = saved[2 * T + 3:]
         fin = rest.pop(0) if ctx.has_fin else None
-        rows = _state_rows(st_all, fin, T)
-        n1 = 2 * B * H * W * C
-        states = [[rows[t][l * n1:(l + 1) * n1].as_strided((2, B, C, H, W), nhwc_state_strides(B, C, H, W))
-                   for l in range(L)] for t in range(T)]
+        _, states = _state_views(eng, st_all, fin, T, B, H, W)
         mem0 = [rest.pop(0) if ctx.has_mem[l] else None for l in range(L)]
         sprev0 = [rest.pop(0) if (ctx.has_prev[l] and eng.rec[l]) else None for l in range(L)]
         mem_in = [mem0] + [[states[t - 1][l][0] for l in range(L)] for t in range(1, T)]
@@ -1587,37 +1473,24 @@ class FireNetSequence(torch.autograd.Function):
         for t in range(T - 1, 0, -1):
             g_out[t] = [empty_state(B, C, H, W, dev) if (eng.rec[l] and l not in chain) else None for l in range(L)]
             g_into[t - 1] = g_out[t]
-        g0 = [None] * L
-        for l in range(L):
-            if not (ctx.has_prev[l] and ctx.needs_input_grad[2 + T + l]):
-                continue
-            if ctx.ext[l]:
-                g0[l] = torch.zeros((2, B, C, H, W), device=dev).as_strided(
-                    (2, B, C, H, W), (B * H * W * C, H * W * C, 1, W * C, C))
-            elif eng.rec[l]:
-                g0[l] = empty_state(B, C, H, W, dev)
+        g0 = _state_input_grads(eng, ctx.has_prev, ctx.needs_input_grad[2 + T:2 + T + L], ctx.ext, B, H, W, dev)
         g_out[0] = g0
         ext = [list(ctx.ext)] + [[False] * L for _ in range(T - 1)]  # only step 0 sees external states
         gmem = [[None] * L for _ in range(T)]
         gmem[0] = [g0[l] if (g0[l] is not None and ctx.ext[l]) else None for l in range(L)]
         gxs = [torch.empty_like(xs[t]) if ctx.needs_input_grad[2 + t] else None for t in range(T)]
-        gfl = []
-        for g in g_flows:
-            if g is not None and (g.stride(3) != 1 or g.stride(2) != W or g.dtype != torch.float32):
-                g = g.contiguous().float()
-            gfl.append(g)
+        gfl = [_flow_grad(g, W) for g in g_flows]
 
         # the deferred weight gradients see the steps in the per-step path's order (last first)
         # layers >= 1: dW inside the backward slot tasks (wslab_*); the forward's choice (it skipped the
         # spike planes the fused form never reads), not the engine flag's value now
         fuse = ctx.fuse
-        # the head's dW inside its backward tasks (ABI 40): a feed-forward 2- / 4-channel head
-        fuse_head = (bool(eng.fuse_head) and not eng.rec[0] and cin0 in (2, 4)
-                     and all(x.dim() == 4 and x.dtype == torch.float32 for x in xs))
+        fuse_head = _fuse_head_ok(eng, cin0, xs)
         bptr = ctx.bptr
         for t in range(T - 1, -1, -1):
-            eng.pending.append((_Rows(gcur[t]), _Rows(bnc[t]), _Rows(ys[t]), _Rows(stats[t]), xs[t], states[t], s_prev[t],
-                                (gcur, bnc, ys, stats, ctx.bits), (bptr[t], bptr[t - 1] if t >= 1 else [None] * L)))
+            eng.pending.append(Pending(_Rows(gcur[t]), _Rows(bnc[t]), _Rows(ys[t]), _Rows(stats[t]), xs[t], states[t],
+                                       s_prev[t], (gcur, bnc, ys, stats, ctx.bits),
+                                       (bptr[t], bptr[t - 1] if t >= 1 else [None] * L)))
             eng.pending_layers.append(tuple(l for l in range(L) if not ((fuse and l > 0) or (fuse_head and l == 0))))
         try:
             # wavefront launches (the chained schedule's are described at chained_bwd_slots):
@@ -1664,14 +1537,8 @@ class FireNetSequence(torch.autograd.Function):
                             a.wslab_accumulate = 1 if eng.slab_live[l] else 0
                             eng.slab_live[l] = True
                         layers.append(a)
-                arr = (_lib.LayerBwdArgs * max(len(layers), 1))(*layers)
-                if chained:
-                    _lib.call("bwd_slot", lib.snnflow_bwd_chain, arr, len(layers),
-                              (ctypes.c_ubyte * max(len(pairs), 1))(*pairs),
-                              ctypes.byref(top) if top is not None else None, s)
-                else:
-                    _lib.call("bwd_slot", lib.snnflow_bwd_slot, arr, len(layers),
-                              ctypes.byref(top) if top is not None else None, s)
+                _slot_call("bwd_slot", lib.snnflow_bwd_chain, lib.snnflow_bwd_slot, chained, _lib.LayerBwdArgs, layers,
+                           pairs, top, s)
             _lib.timer_close()
             for l in range(L):
                 for t in range(T):
@@ -1679,19 +1546,13 @@ class FireNetSequence(torch.autograd.Function):
             if ctx.root:
                 eng.flush_weight_grads(B, H, W, cin0, ws, glayers, s)
         except Exception:
-            ws.reset_acc()
-            eng.bwd_open = False
-            eng.pending, eng.pending_layers = [], []
-            eng.prep_stale = True
+            eng.abort_backward()
             raise
 
         pgrads = [None] * len(eng.flat_layout)
         if ctx.root:
             pgrads = [eng.flat[o:o + n].view(shp) for o, n, shp in eng.flat_layout]
-            eng.flat_views = None
-            eng.bwd_open = False
-            eng.last_flat = eng.flat
-            eng.prep_stale = True
+            eng.close_chain()
         return (None, None, *gxs, *g0, *pgrads)
 
 
@@ -1724,30 +1585,14 @@ def eval_sequence(eng, xs, prev):
     summation order.  Returns (flows [T], final states [L]); no autograd."""
     L, C = eng.L, eng.C
     T = len(xs)
-    B, cin0, H, W = xs[0].shape
+    B, cin0, H, W = _same_shape_inputs(xs)
     dev = xs[0].device
-    for x in xs:
-        _lib.require_device(x, "event tensor")
-        if tuple(x.shape) != (B, cin0, H, W):
-            raise _lib.SnnflowError("forward_sequence: every step's input must have the same shape")
     s = _lib.stream_ptr(dev)
     wfwd, wbwd = eng.prep_weights(s, refresh=eng.prep_stale)
     eng.prep_stale = False
     neurons = eng.neurons()
     n1 = 2 * B * H * W * C
-    fin = eng.final_state_out
-    eng.final_state_out = None
-    if fin is not None:
-        if (fin.device != dev or fin.dtype != torch.float32 or fin.numel() != L * n1 or not fin.is_contiguous()
-                or any(p is not None and p.untyped_storage().data_ptr() == fin.untyped_storage().data_ptr()
-                       for p in prev)):
-            raise _lib.SnnflowError("final_state_out: a contiguous fp32 buffer of L*2*B*H*W*C floats on the "
-                                    "input's device, not aliasing the initial states")
-        fin = fin.view(L * n1)
-    st_all = torch.empty(T - (fin is not None), L * n1, device=dev)
-    rows = _state_rows(st_all, fin, T)
-    sst = nhwc_state_strides(B, C, H, W)
-    states = [[rows[t][l * n1:(l + 1) * n1].as_strided((2, B, C, H, W), sst) for l in range(L)] for t in range(T)]
+    _, _, rows, states = _window_states(eng, T, B, H, W, dev, prev)
     flows = [torch.empty(B, 2, H, W, device=dev) for _ in range(T)]
     half = 4 * (n1 // 2)
     keep, mem0, sp0 = [], [], []

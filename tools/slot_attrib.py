@@ -3,7 +3,7 @@
     python tools/slot_attrib.py <counter_collection.csv | kernel_trace.csv> [fwd|fwdchain|bwd|bwdchain] [T] > out.json
 
 Every slot launch of a LIFFireNet window holds a known mix of layer-steps (task (k, t) in launch
-k + 2t, engine.wavefront_slots), so a per-dispatch quantity -- a PMC counter, or the duration from a
+k + 2t, schedule.wavefront_slots), so a per-dispatch quantity -- a PMC counter, or the duration from a
 kernel trace -- regressed on the launch's task mix (non-negative least squares) gives each task kind's
 marginal share: which layer-step kind carries the LDS bank conflicts, the VALU instructions or the
 time.  Dispatches of one pass are taken in order, 2(T-1)+L+1 per pass (LIFFireNet: L = 7 cells, the
@@ -13,11 +13,11 @@ Task kinds, backward (launch d: j + 2 tau = d, j = 0 top, j >= 1 layer L - j, st
   top (pred + LIF backward of layer 6), ff (LIF-fed feed-forward layer with its fused weight
   gradient), rec (recurrent layer, t >= 1: packed dW_ff | dW_rec), rec0 (recurrent layer at t = 0:
   no s_prev), head (layer 0: one block).
-bwdchain: the chained backward schedule (engine.chained_bwd_slots, T + L launches): the same kinds plus
+bwdchain: the chained backward schedule (schedule.chained_bwd_slots, T + L launches): the same kinds plus
   pair (the recurrent task (r, t+1) and the feed-forward task (r+1, t) in one block per tile).
 Forward (launch d: k + 2t = d): head (conv of the event counts), ff (LIF of layer k-1 + conv k),
 rec (the same + the recurrent conv), top (LIF of layer 6 + pred).
-fwdchain: the chained forward schedule (engine.chained_fwd_slots, T + L launches): head, ff, rec0 (the
+fwdchain: the chained forward schedule (schedule.chained_fwd_slots, T + L launches): head, ff, rec0 (the
   recurrent layer's task of step 0, the only one left on its own), top, plus pair (the feed-forward task
   (r+1, t-1) and the recurrent task (r, t) in one block per tile) -- set a pair's figure against ff + rec
   of the plain fit for what the pair costs against the sum of its halves.
