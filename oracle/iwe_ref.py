@@ -175,7 +175,8 @@ class EventWarpingRef:
         self.maps.append(flow)
         self._passes += 1
 
-    def _iwe_term(self, events, flow_ev, pol4, tsw, tref):
+    def _iwe_parts(self, events, flow_ev, pol4, tsw, tref):
+        """One warp direction: the four IWEs (cnt+, cnt-, ts+, ts-) and per sample S+, S-, nz, loss_b."""
         idx, w = get_interpolation_t(events, flow_ev, tref, self.res, self.flow_scaling)
         cnt_p = interpolate_t(idx, w, self.res, pol4[:, :, 0:1])
         cnt_n = interpolate_t(idx, w, self.res, pol4[:, :, 1:2])
@@ -184,12 +185,17 @@ class EventWarpingRef:
         T = self._passes
         a = (ts_p / (cnt_p + 1e-9) / T).reshape(events.shape[0], -1)
         b = (ts_n / (cnt_n + 1e-9) / T).reshape(events.shape[0], -1)
-        per_sample = torch.sum(a ** 2, dim=1) + torch.sum(b ** 2, dim=1)
+        s_p, s_n = torch.sum(a ** 2, dim=1), torch.sum(b ** 2, dim=1)
+        per_sample = s_p + s_n
+        nz = (cnt_p + cnt_n).clone()
+        nz[nz > 0] = 1
+        nz = torch.sum(nz.reshape(events.shape[0], -1), dim=1)
         if self.loss_scaling:
-            nz = (cnt_p + cnt_n).clone()
-            nz[nz > 0] = 1
-            per_sample = per_sample / torch.sum(nz.reshape(events.shape[0], -1), dim=1)
-        return torch.sum(per_sample)
+            per_sample = per_sample / nz
+        return (cnt_p, cnt_n, ts_p, ts_n), (s_p, s_n, nz, per_sample)
+
+    def _iwe_term(self, events, flow_ev, pol4, tsw, tref):
+        return torch.sum(self._iwe_parts(events, flow_ev, pol4, tsw, tref)[1][3])
 
     def overwrite_intermediate_flow(self, flow_list):
         """``loss/flow.py:123-150``: re-gather every event's flow from the final map,
@@ -208,13 +214,20 @@ class EventWarpingRef:
         self.maps = [flow]
 
     def __call__(self):
+        return self.terms()["loss"]
+
+    def terms(self):
+        """What ``__call__`` computes, with its intermediate results: ``images`` [2 dir][4 img][B][H W]
+        (cnt+, cnt-, ts+, ts- of the forward and the backward warp), ``persample`` [2][B][4] (S+, S-, nz,
+        loss_b), ``smooth`` [5] (the Charbonnier sums dx, dy, dr, ur, dt; dt = 0 where it is skipped) and
+        ``loss`` (the autograd scalar)."""
         T = self._passes
         events = torch.cat(self.events, dim=1)
         flow_ev = torch.cat(self.flows_ev, dim=1)
         pol4 = torch.cat([torch.cat(self.pols, dim=1)] * 4, dim=1)
         ts4 = torch.cat([events[:, :, 0:1]] * 4, dim=1)
-        fw = self._iwe_term(events, flow_ev, pol4, ts4, T)
-        bw = self._iwe_term(events, flow_ev, pol4, T - ts4, 0)
+        parts = [self._iwe_parts(events, flow_ev, pol4, ts4, T), self._iwe_parts(events, flow_ev, pol4, T - ts4, 0)]
+        fw, bw = torch.sum(parts[0][1][3]), torch.sum(parts[1][1][3])
 
         fx = torch.cat([m[:, 0:1] for m in self.maps], dim=1)
         fy = torch.cat([m[:, 1:2] for m in self.maps], dim=1)
@@ -239,8 +252,14 @@ class EventWarpingRef:
             if self.smoothing_mask:
                 d = (em[a] * em[b]) * d
             terms.append(d)
-        smooth = terms[0].sum()
-        for t in terms[1:]:
-            smooth = smooth + t.sum()
+        sums = [t.sum() for t in terms]
+        smooth = sums[0]
+        for t in sums[1:]:
+            smooth = smooth + t
         smooth = smooth / len(terms) / fx.shape[1]  # flow_dx.shape[1]: number of flow maps (flow.py:293)
-        return fw + bw + self.weight * smooth
+        B = events.shape[0]
+        with torch.no_grad():
+            images = torch.stack([torch.stack([im.reshape(B, -1) for im in p[0]]) for p in parts])
+            persample = torch.stack([torch.stack(list(p[1]), dim=1) for p in parts])
+            five = torch.stack([s.detach() for s in sums] + [torch.zeros((), dtype=fx.dtype)] * (5 - len(sums)))
+        return {"images": images, "persample": persample, "smooth": five, "loss": fw + bw + self.weight * smooth}
